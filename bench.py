@@ -13,12 +13,19 @@ hash-sharded over the ranks (10M elements per rank), each rank owns its own
 4096-program slice of the batch (weak scaling), records are routed to their
 owner with RCCL all-to-all (syzkaller_amd/dist.py).
 
-Prints one JSON line on rank 0.  Beside the headline K3 line it carries, as
-their own objects with their own roofline, `lines.edge` (K1+K2: KCOV PCs ->
-edge signals, 12 B/PC) and `lines.minimize` (BASELINE config 3: Minimize over
-a 200k-context corpus, 5 B/entry + 4 B/distinct element); `cpu_baseline` is
+Prints one JSON line on rank 0.  A plain run sets up, warms up, times the
+steps and prints the headline K3 line (value, ms_per_step, the K3 stage times
+of the timed steps).  --dump-outputs DIR also writes what the last timed step
+returned (dump_outputs) as DIR/<name>.npy.
+
+--full adds everything that takes runs of its own: the achievable HBM
+bandwidth, the PMC traffic of the rooflines, and, as their own objects with
+their own roofline, `lines.edge` (K1+K2: KCOV PCs -> edge signals, 12 B/PC),
+`lines.minimize` (BASELINE config 3: Minimize over a 200k-context corpus,
+5 B/entry + 4 B/distinct element) and the other `lines.*`; `cpu_baseline` is
 the oracle on one core plus `multi_core` (--cpu-threads Procs under one
-rwlock, as syz-fuzzer runs checkNewSignal), with nproc and the CPU model.
+rwlock, as syz-fuzzer runs checkNewSignal), with nproc and the CPU model; with
+N > 1 the `parity` check against the oracle.
 """
 import argparse
 import json
@@ -62,6 +69,11 @@ def parse():
     ap.add_argument("--m0-total", type=int, default=1_000_000_000,
                     help="N>1: maxSignal elements over all ranks, hash-sharded (BASELINE config 4: 1B)")
     ap.add_argument("--skew", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the achievable bandwidth, PMC traffic, stages.edge_ms/ingest_ms, every "
+                         "lines.* entry, the CPU baselines, and (N>1) the parity check; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time (s)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
@@ -84,7 +96,10 @@ def parse():
     ap.add_argument("--batches", type=int, default=4, help="distinct batches the steps cycle through")
     ap.add_argument("--no-pipe", action="store_true", help="skip the K1+K2 -> K3 pipeline line")
     ap.add_argument("--no-poll", action="store_true", help="skip the manager Poll line")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 TRIAGE_KEYS = ("programs_per_gpu", "calls", "pcs_per_call", "m0_per_gpu", "skew", "parallelism", "walk", "batches")
@@ -867,6 +882,52 @@ def dist_parity(dev, sharded, batch, pool0, pairs, reset, ns, m0e, m0p, rank, wo
     return out
 
 
+DUMP_SEED = 20181  # the sample of an output too large to write whole
+DUMP_MAX_SIGNAL, DUMP_NEW_SIGNAL, DUMP_PAIRS = 2_000_000, 1_000_000, 2_000_000  # entries kept (<= 56 MB in all)
+
+
+def dump_sample(n, cap):
+    """The positions kept of an n-entry output: all of them, or a fixed
+    (DUMP_SEED) sorted sample of `cap`."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(path, suffix, ms, ns, pairs, call_new, st):
+    """What a caller of the timed step holds after it (checkNewSignal over the
+    batch, syz-fuzzer/fuzzer.go:494-511), as <name><suffix>.npy under `path`:
+      call_new            float32[ncalls]  1 where the call had new signal
+      new_pairs           float64[k]       the DiffRaw entries (call << 32 | elem), ascending
+      max_signal_elems    float64[k], max_signal_prios float32[k]   maxSignal after the step, by element
+      new_signal_elems    float64[k], new_signal_prios float32[k]   newSignal of the step, by element
+      counts              float64[4]       len(maxSignal), len(newSignal), DiffRaw entries, calls with new signal
+    The sets and the pairs are sorted first (their order in memory is not
+    part of the result); one longer than its DUMP_* cap is written as the
+    dump_sample positions of the sorted whole."""
+    os.makedirs(path, exist_ok=True)
+
+    def put(name, arr, dtype):
+        np.save(os.path.join(path, name + suffix + ".npy"), np.ascontiguousarray(arr, dtype=dtype))
+
+    cn = call_new.cpu().numpy()
+    put("call_new", cn, np.float32)
+    npairs = min(int(st["new_pairs"]), pairs.numel())
+    p = torch.sort(pairs[:npairs]).values
+    idx = dump_sample(npairs, DUMP_PAIRS)
+    put("new_pairs", p[torch.from_numpy(idx).to(p.device)].cpu().numpy().view(np.uint64), np.float64)
+    lens = []
+    for name, s, cap in (("max_signal", ms, DUMP_MAX_SIGNAL), ("new_signal", ns, DUMP_NEW_SIGNAL)):
+        ser = s.Serialize()
+        e, pr = np.asarray(ser.Elems), np.asarray(ser.Prios)
+        order = np.argsort(e, kind="stable")
+        keep = order[dump_sample(e.size, cap)]
+        put(name + "_elems", e[keep], np.float64)
+        put(name + "_prios", pr[keep], np.float32)
+        lens.append(e.size)
+    put("counts", [lens[0], lens[1], int(st["new_pairs"]), int(np.count_nonzero(cn))], np.float64)
+
+
 def progress(rank, msg):
     """One line per setup phase on stderr (a silent multi-minute setup looks hung)."""
     print(f"[bench rank {rank}] {msg} (t={time.perf_counter() - T0:.1f}s)", file=sys.stderr, flush=True)
@@ -902,7 +963,7 @@ def main():
     progress(rank, f"device {local}, world {world}")
     dev = Device(local)
     dev.L.syzsig_ctx_set_timing(dev.eng.h, 1)
-    ach = achievable_bw(dev)
+    ach = achievable_bw(dev) if a.full else None
     cfg = walk_cfg(a.walk, skew=a.skew)
     known = KNOWN_SYS[a.walk]
     P, C, L = a.programs, a.calls, a.pcs
@@ -916,7 +977,7 @@ def main():
     cnt = torch.empty(P * C, dtype=torch.int32, device=dev.dev)
     comp = torch.empty(P, dtype=torch.int32, device=dev.dev)
     edge_ms, edge_dev_ms = [], []
-    for i in range(3):
+    for i in range(3 if a.full else 1):  # (once derives the batch; --full times it as stages.edge_ms)
         torch.cuda.synchronize()
         t = time.perf_counter()
         dev.edge_derive(pcs, cs, cl, pidx, sigs, cnt, comp)
@@ -1018,6 +1079,10 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     total_rec = sum(s["nrec"] for s in stats)  # this rank's records over the timed steps
+    if a.dump_outputs:
+        progress(rank, f"outputs of the last step -> {a.dump_outputs}")
+        dump_outputs(a.dump_outputs, f"_rank{rank}" if distributed else "", ms, ns, pairs,
+                     batches[(a.warmup + a.steps - 1) % NB][2], stats[-1])
     reset()  # (outside the timed region: the reset brought back M0 exactly)
     restore_ok = ms.equal(pristine)
     if not restore_ok:
@@ -1030,8 +1095,9 @@ def main():
         dist.all_reduce(tr)
         total_rec = int(tr.item())
     parity = dist_parity(dev, sharded, batches[0], pool[0], pairs, reset, ns, m0e, m0p, rank, world, P, C,
-                         a.dist_backend) if distributed else None
-    ingest_ms, ingest_ok = ingest_stage(dev, sigs, cs, cnt, prio, comp, P, C) if not distributed else (None, None)
+                         a.dist_backend) if distributed and a.full else None
+    ingest_ms, ingest_ok = ingest_stage(dev, sigs, cs, cnt, prio, comp, P, C) \
+        if a.full and not distributed else (None, None)
     ms_per_step = dt / a.steps * 1e3
     value = total_rec / dt
     s0 = stats[-1]
@@ -1080,16 +1146,20 @@ def main():
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "bytes_per_unit": PROBE_BYTES_PER_REC, "units_per_launch": probe_units,
                          "avg_launch_ms": k3_ms},
-            "stages": {"edge_ms": float(np.median(edge_ms)), "edge_dev_ms": float(np.median(edge_dev_ms)), "part_ms": part_ms, "agg_ms": probe_ms,
+            # (edge_* and ingest_* are timed by --full alone: a plain run derives the batch once, cold)
+            "stages": {"edge_ms": float(np.median(edge_ms)) if a.full else None,
+                       "edge_dev_ms": float(np.median(edge_dev_ms)) if a.full else None,
+                       "part_ms": part_ms, "agg_ms": probe_ms,
                        "finalize_ms": decide_ms,
-                       "edge_pcs_per_s": npc / (np.median(edge_ms) * 1e-3),
+                       "edge_pcs_per_s": npc / (np.median(edge_ms) * 1e-3) if a.full else None,
                        "ingest_ms": ingest_ms, "ingest_check": ingest_ok},
             "triage": {k: v for k, v in s0.items() if k not in ("probe_ms", "decide_ms", "part_ms", "nrec")},
             "state_reset": "maxSignal back to M0 before every step: a table copy, or the slots of the previous "
                            "step's newSignal elements (syzsig_set_restore_keys) when that moves fewer bytes; "
                            "checked equal to M0 after the timed steps",
         }
-    if rank == 0:
+    full0 = rank == 0 and a.full  # everything below the headline takes runs (or look-ups) of its own
+    if full0:
         traffic, src, note = pmc_traffic(["syz::" + k for k in (K3_KERNELS if not distributed else K3_DIST_KERNELS)
                                           .split("+")], out["config"], expect_ms=k3_ms)
         out["roofline"]["traffic"] = traffic
@@ -1108,35 +1178,36 @@ def main():
                          "unit": "GB/s", "frac": e_ach / HBM_PEAK_GBS, "traffic": e_traffic, "traffic_source": e_src,
                          "traffic_note": e_note,
                          "bytes_per_unit": EDGE_BYTES_PER_PC, "units_per_launch": npc, "avg_launch_ms": e_ms}}}
-    if rank == 0 and world == 1 and not a.no_min:
+    if full0 and world == 1 and not a.no_min:
         out["lines"]["minimize"] = minimize_line(dev, a.min_contexts, cpu_s=0 if a.no_cpu else a.cpu_seconds / 3)
-    if rank == 0 and world == 1 and not a.no_c5:
+    if full0 and world == 1 and not a.no_c5:
         out["lines"]["c5"] = c5_line(dev, pairs, cpu_s=0 if a.no_cpu else a.cpu_seconds / 3,
                                      cpu_threads=a.cpu_threads)
         # rounds 1-4's C5 input (power-skewed region walks), kept comparable
         out["lines"]["c5_region_power"] = c5_line(dev, pairs, walk="region")
-    if rank == 0 and world == 1 and not a.no_pipe:
+    if full0 and world == 1 and not a.no_pipe:
         out["lines"]["pipeline"] = pipeline_line(dev, pairs, P, C, L, a.walk)
-    if rank == 0 and world == 1 and not a.no_gw:
+    if full0 and world == 1 and not a.no_gw:
         other = "region" if a.walk == "global" else "global"
         out["lines"][f"c2_{other}_walk"] = c2_walk_line(dev, pairs, P, C, L, other)
-    if rank == 0 and world == 1 and not a.no_c1:
+    if full0 and world == 1 and not a.no_c1:
         out["lines"]["c1"] = c1_line(dev)
-    if rank == 0 and world == 1 and not a.no_poll:
+    if full0 and world == 1 and not a.no_poll:
         out["lines"]["poll"] = poll_line(dev, cpu_s=0 if a.no_cpu else a.cpu_seconds / 3)
-    if rank == 0 and world == 1 and not a.no_c4:
+    if full0 and world == 1 and not a.no_c4:
         out["lines"]["c4_rank"] = c4_rank_line(dev, sigs, cs, cnt, prio, P, C, L, a.walk)
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if full0 and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline(dev, sigs, cs, cnt, prio, m0e, m0p, C, a.cpu_seconds, a.cpu_threads)
-    elif rank == 0:
+    elif full0:
         out["cpu_baseline"] = None
-    if rank == 0 and distributed:
+    if full0 and distributed:
         out["parity"] = parity
-    if rank == 0:
+    if full0:
         out["achievable_bw"] = ach
         with_achievable(out["roofline"], ach)
         for ln in out["lines"].values():
             with_achievable(ln.get("roofline"), ach)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if distributed:
         dist.destroy_process_group()

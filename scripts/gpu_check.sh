@@ -17,5 +17,5 @@ step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
 rc=$?; [ $rc -gt 1 ] && exit $rc
 step pytest_gpu 1000 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ${PYTEST_ARGS:-}
 rc=$?; [ $rc -gt 1 ] && exit $rc
-step bench 600 python -u bench.py --steps "$STEPS" --warmup 1
+step bench 600 python -u bench.py --full --steps "$STEPS" --warmup 1
 exit $?

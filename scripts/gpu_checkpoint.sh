@@ -13,4 +13,4 @@ step() {
 }
 step tests 700 python -u -m pytest -q --timeout 400 --timeout-method thread -m gpu tests || exit $?
 step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step bench 300 python -u bench.py
+step bench 300 python -u bench.py --full

@@ -9,7 +9,7 @@ mkdir -p $O
 [ "${SKIP_TESTS:-0}" = 1 ] || SYZSIG_LIB=${TEST_LIB:-syzkaller_amd/libsyzsig.so} timeout -k 10 600 python -u -m pytest -x -q --timeout 500 --timeout-method thread -m gpu tests/test_gpu_edge.py \
 	tests/test_gpu_edge_c2.py > $O/tests.log 2>&1
 rc=$?; echo "[tests] exit $rc" >> $O/status.log; [ $rc -ne 0 ] && exit $rc
-A="--steps 2 --warmup 1 --no-cpu --no-min --no-c5 --no-c4 --no-c1 --no-gw --no-pipe --batches 1"
+A="--full --steps 2 --warmup 1 --no-cpu --no-min --no-c5 --no-c4 --no-c1 --no-gw --no-pipe --batches 1"
 for rep in 1 2; do
 	for v in ${VARIANTS:-dec dec0}; do
 		L=syzkaller_amd/libsyzsig.so; [ $v != dec ] && L=exp/libsyzsig_$v.so

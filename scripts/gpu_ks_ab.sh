@@ -13,7 +13,7 @@ done
 for rep in 1 2; do
 	for k in base ${KS_LIST:-ks2 ks3}; do
 		if [ $k = base ]; then L=syzkaller_amd/libsyzsig.so; else L=exp/libsyzsig_$k.so; fi
-		SYZSIG_LIB=$L timeout -k 10 200 python -u bench.py --steps 3 --warmup 1 --no-cpu --no-min --no-c5 --no-c4 --no-c1 --no-gw --no-pipe > $O/b_${k}_$rep.log 2>&1; rc=$?; st b_${k}_$rep $rc; [ $rc -ne 0 ] && exit $rc
+		SYZSIG_LIB=$L timeout -k 10 200 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --no-min --no-c5 --no-c4 --no-c1 --no-gw --no-pipe > $O/b_${k}_$rep.log 2>&1; rc=$?; st b_${k}_$rep $rc; [ $rc -ne 0 ] && exit $rc
 	done
 done
 exit 0

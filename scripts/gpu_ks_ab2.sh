@@ -11,7 +11,7 @@ for v in ${VARIANTS:-ks2 ks3}; do
 		tests/test_gpu_edge.py tests/test_gpu_edge_c2.py > $O/tests_$v.log 2>&1
 	rc=$?; echo "[tests $v] exit $rc" >> $O/status.log; [ $rc -ne 0 ] && exit $rc
 done
-A="--steps 2 --warmup 1 --no-cpu --no-min --no-c5 --no-c4 --no-c1 --no-gw --no-pipe --batches 1"
+A="--full --steps 2 --warmup 1 --no-cpu --no-min --no-c5 --no-c4 --no-c1 --no-gw --no-pipe --batches 1"
 for rep in 1 2; do
 	for v in base ${VARIANTS:-ks2 ks3}; do
 		L=syzkaller_amd/libsyzsig.so; [ $v != base ] && L=exp/libsyzsig_$v.so

@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/parts
 mkdir -p $O
-A="--steps 10 --warmup 4 --no-cpu --no-c5 --no-c4 --no-c1 --no-gw --no-pipe"
+A="--full --steps 10 --warmup 4 --no-cpu --no-c5 --no-c4 --no-c1 --no-gw --no-pipe"
 for rep in 1 2; do
 	for v in base p1024 p1024n; do
 		case $v in

@@ -14,4 +14,4 @@ step() {
 step tests 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu \
 	tests/test_gpu_triage.py tests/test_gpu_minimize_shard.py tests/test_gpu_edge.py ${QUICK_TESTS:-} || exit $?
 step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step bench 300 python -u bench.py --steps 10 --warmup 2 --no-cpu ${BENCH_EXTRA:-}
+step bench 300 python -u bench.py --full --steps 10 --warmup 2 --no-cpu ${BENCH_EXTRA:-}

@@ -10,7 +10,7 @@ O=gpurun_out/recs_ab
 mkdir -p $O
 timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread -m gpu -k "records_mode or restore_keys" tests/test_gpu_triage.py > $O/tests.log 2>&1
 rc=$?; echo "[tests] exit $rc $(tail -1 $O/tests.log)" | tee -a $O/status.log; [ $rc -ne 0 ] && exit $rc
-A="--steps 3 --warmup 1 --no-min --no-c5 --no-c1 --no-cpu"
+A="--full --steps 3 --warmup 1 --no-min --no-c5 --no-c1 --no-cpu"
 c4() { tail -1 "$1" | python3 -c "import json,sys; c=json.loads(sys.stdin.read())['lines']['c4_rank']; print('c4_rank ms %.3f source %.3f owner %.3f' % (c['ms'], c['source_ms'], c['owner_ms']))"; }
 for r in ${RUNS-1 2}; do
 	for v in ${VS:-0 1024}; do

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/sweep
-ARGS=${BENCH_ARGS:---steps 5 --warmup 1 --no-cpu}
+ARGS=${BENCH_ARGS:---full --steps 5 --warmup 1 --no-cpu}
 i=0
 while read -r envs; do
 	[ -z "$envs" ] && continue
