@@ -42,7 +42,7 @@ extern "C" {
 #define SYZSIG_ERANGE (-34)    /* a size limit of this ABI exceeded */
 #define SYZSIG_ECORRUPT (-74)  /* panic("corrupted Serial"), pkg/signal/signal.go:60-62 */
 
-#define SYZSIG_ABI_VERSION 4
+#define SYZSIG_ABI_VERSION 5
 
 typedef struct syzsig_ctx syzsig_ctx;
 typedef struct syzsig_set syzsig_set;
@@ -61,8 +61,9 @@ void* syzsig_ctx_stream(syzsig_ctx* ctx);
 int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
 /* With timing on: device time (ms, HIP events on the context stream) of the
  * kernels of the last syzsig_edge_derive_dev / syzsig_minimize_dev call, or the
- * stream work of the last syzsig_manager_poll_batch call (uploads to its last
- * kernel, including the host round trips between). */
+ * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev or
+ * syzsig_triage_cover_dev call (uploads / first kernel to its last kernel,
+ * including the host round trips between). */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
 /* Measurement: a plain device copy of `bytes` (16-B aligned buffers and size)
  * on the context stream, 16 B per lane per step; *ms = its device time (HIP
@@ -353,6 +354,53 @@ int syzsig_triage_batch(syzsig_ctx* ctx, syzsig_set* max_signal, syzsig_set** ne
 int syzsig_edge_derive_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uint64_t npc, const uint64_t* d_call_start,
                            const uint32_t* d_call_len, uint64_t ncalls, const uint32_t* d_prog_call,
                            uint64_t nprog, uint32_t* d_sigs, uint32_t* d_sig_cnt, uint32_t* d_completed);
+
+/* ---- executor/executor.h:514-527 on device: the call's cover output ----
+ * The second half of write_coverage_signal over the traces of
+ * syzsig_edge_derive_dev (same d_pcs .. nprog arguments and limits), with
+ * flag_collect_cover on.  d_completed (required) is what syzsig_edge_derive_dev
+ * wrote for the same traces: call c of program p has a cover record iff
+ * c - prog_call[p] < completed[p]; the aborting call and every later one get
+ * cover_cnt = 0 and nothing written (doexit(0) precedes any cover write).
+ * flags: SYZSIG_COVER_DEDUP = flag_dedup_cover, the PCs sorted ascending and
+ * made unique before the truncation to u32 (the fuzzer's triage executions,
+ * proc.go:49-50, :250); without it the truncated PCs in trace order,
+ * cover_cnt = call_len.  Call c's cover lands at d_cover[call_start[c] ..
+ * +cover_cnt[c]) (d_cover has npc entries, indexed like d_pcs; words outside
+ * those ranges are left alone); d_cover_cnt has ncalls entries.  Rejects
+ * (SYZSIG_EINVAL, nothing written) NULL arguments, a call_len >= 262144, a
+ * range outside [0, npc), and a completed[p] above program p's calls.
+ * SYZSIG_COVER_TILE: a segment of at most this many keys is sorted in LDS by
+ * one workgroup; a longer one goes through the context's workspace in HBM. */
+#define SYZSIG_COVER_DEDUP 1u
+#define SYZSIG_COVER_TILE 4096
+int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uint64_t npc, const uint64_t* d_call_start,
+                          const uint32_t* d_call_len, uint64_t ncalls, const uint32_t* d_prog_call, uint64_t nprog,
+                          const uint32_t* d_completed, uint32_t flags, uint32_t* d_cover, uint32_t* d_cover_cnt);
+
+/* ---- syz-fuzzer/proc.go:139 inputCover.Merge(inf.Cover) and :173 Cover:
+ * inputCover.Serialize(), over the item / run layout of syzsig_triage_runs_dev ----
+ * Run r = i * runs + k of item i has the cover list d_cover[run_cover_start[r]
+ * .. +run_cover_len[r]) (ranges inside one u32 buffer of ncover words: the
+ * output of syzsig_edge_cover_dev, or the executor regions with the
+ * cover_start / cover_len of syzsig_ingest_exec_output_dev).  Item i's
+ * inputCover is the set union of the lists of its runs that the loop did not
+ * skip (a run is skipped when run_exec == 0, its signal is empty --
+ * run_off[r + 1] == run_off[r], the only use of d_run_off -- or
+ * SYZSIG_TRIAGE_ORIG_OK is set and run_errno != 0; proc.go:122-123), and empty
+ * when item_keep[i] == 0 (as syzsig_triage_runs_dev wrote it: every `return`
+ * of the loop precedes :173).  Item i's PCs are written sorted ascending (one
+ * fixed instance of Serialize's map order) to
+ * d_item_cover[item_cover_off[i] .. item_cover_off[i + 1]); item_cover_off has
+ * nitems + 1 entries; *n_out = the total.  If it exceeds cap (the capacity of
+ * d_item_cover in entries) nothing is written: SYZSIG_ERANGE with the needed
+ * total in *n_out.  An item's merged lists hold fewer than 2^31 PCs
+ * (SYZSIG_ERANGE); a cover range outside [0, ncover) is SYZSIG_EINVAL. */
+int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_t runs, const uint8_t* d_item_flags,
+                            const uint8_t* d_item_keep, const uint64_t* d_run_off, const int32_t* d_run_errno,
+                            const uint8_t* d_run_exec, const uint32_t* d_cover, uint64_t ncover,
+                            const uint64_t* d_run_cover_start, const uint32_t* d_run_cover_len,
+                            uint64_t* d_item_cover_off, uint32_t* d_item_cover, uint64_t cap, uint64_t* n_out);
 
 /* ---- pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output regions ----
  * Program p's output region (executor.h:566-604 records, the executor's shmem

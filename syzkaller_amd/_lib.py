@@ -25,6 +25,8 @@ SYZSIG_DEBUG_EDGE_MARKALL = 1024
 SYZSIG_DEBUG_EDGE_PASSES = 2048
 SYZSIG_DEBUG_POLL_FAIL = 4096
 SYZSIG_DEBUG_AGG_IDX64 = 8192
+SYZSIG_COVER_DEDUP = 1
+SYZSIG_COVER_TILE = 4096  # include/syzsig.h: longer segments leave the one-workgroup LDS sort
 
 
 class SyzsigError(RuntimeError):
@@ -130,6 +132,9 @@ SIGNATURES = {
                                         POINTER(c_uint32), _P]),
     "syzsig_triage_batch": (c_int, [_P, _P, _PP, POINTER(Batch), POINTER(BatchStats)]),
     "syzsig_edge_derive_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, _P, _P]),
+    "syzsig_edge_cover_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, c_uint32, _P, _P]),
+    "syzsig_triage_cover_dev": (c_int, [_P, c_uint64, c_uint32, _P, _P, _P, _P, _P, _P, c_uint64, _P, _P, _P, _P,
+                                        c_uint64, POINTER(c_uint64)]),
     "syzsig_ingest_exec_output_dev": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P, _P, _P, _P,
                                               _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_triage_records_dev": (c_int, [_P, _P, _PP, _P, c_uint64, _P, c_uint32, _P,

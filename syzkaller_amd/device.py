@@ -130,6 +130,22 @@ class Device:
                                             _p(completed)))
         return sigs, sig_cnt, completed
 
+    def edge_cover(self, pcs, call_start, call_len, prog_call, completed, dedup=True, cover=None, cover_cnt=None):
+        """executor.h:514-527 for every call of a batch (syzsig_edge_cover_dev):
+        the cover output of the traces edge_derive took, `completed` as it
+        returned it.  dedup = flag_dedup_cover.  Returns (cover int32[npc], call
+        c's at cover[call_start[c] : +cover_cnt[c]], cover_cnt int32[ncalls])."""
+        self._check_dev(pcs, call_start, call_len, prog_call, completed, cover, cover_cnt)
+        nprog = prog_call.numel() - 1
+        if cover is None:
+            cover = torch.empty(pcs.numel(), dtype=torch.int32, device=self.dev)
+        if cover_cnt is None:
+            cover_cnt = torch.empty(call_len.numel(), dtype=torch.int32, device=self.dev)
+        check(self.L.syzsig_edge_cover_dev(self.eng.h, _p(pcs), pcs.numel(), _p(call_start), _p(call_len),
+                                           call_len.numel(), _p(prog_call), max(nprog, 0), _p(completed),
+                                           _lib.SYZSIG_COVER_DEDUP if dedup else 0, _p(cover), _p(cover_cnt)))
+        return cover, cover_cnt
+
     # ---------------------------------------------------------------- executor output ingest
     def ingest_exec_output(self, out, prog_off, prog_call, call_any, call_num=None, want_cover=False):
         """pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output
@@ -163,10 +179,14 @@ class Device:
 
     # ---------------------------------------------------------------- triageInput re-runs
     def triage_runs(self, item_off, elems, prios, item_flags, runs, run_off, run_sigs, run_prio, run_errno,
-                    run_exec):
+                    run_exec, cover=None):
         """syz-fuzzer/proc.go:107-140 over a batch of triage items (see
         include/syzsig.h syzsig_triage_runs_dev).  Returns (item_keep, elem_keep)
-        as uint8 device tensors."""
+        as uint8 device tensors.  With cover = (cover, run_cover_start,
+        run_cover_len) -- the runs' cover lists, see triage_cover -- it also
+        returns the items' inputCover (proc.go:139) as a list: entry i is the
+        slice of sorted PCs for RPCInput.Cover (:173) of a kept item, None for
+        a dropped one."""
         self._check_dev(item_off, elems, prios, item_flags, run_off, run_sigs, run_prio, run_errno, run_exec)
         nitems = item_off.numel() - 1
         if run_off.numel() != nitems * runs + 1 and nitems > 0:
@@ -176,7 +196,39 @@ class Device:
         check(self.L.syzsig_triage_runs_dev(self.eng.h, _p(item_off), max(nitems, 0), _p(elems), _p(prios),
                                             _p(item_flags), int(runs), _p(run_off), _p(run_sigs), _p(run_prio),
                                             _p(run_errno), _p(run_exec), _p(item_keep), _p(elem_keep)))
-        return item_keep, elem_keep
+        if cover is None:
+            return item_keep, elem_keep
+        off, item_cover = self.triage_cover(item_flags, item_keep, runs, run_off, run_errno, run_exec, *cover)
+        o, k = off.cpu().tolist(), item_keep.cpu().tolist()
+        return item_keep, elem_keep, [item_cover[o[i]:o[i + 1]] if k[i] else None for i in range(max(nitems, 0))]
+
+    def triage_cover(self, item_flags, item_keep, runs, run_off, run_errno, run_exec, cover, run_cover_start,
+                     run_cover_len, item_cover=None):
+        """triageInput's inputCover (proc.go:139, :173) per item, over the layout
+        of triage_runs (syzsig_triage_cover_dev): run r's cover list is
+        cover[run_cover_start[r] : +run_cover_len[r]] (int64 / int32 tensors of
+        nitems * runs entries; `cover` is an edge_cover output or the executor
+        regions the ingest indexed).  Returns (item_cover_off int64[nitems + 1],
+        item_cover int32[total]): item i's PCs, sorted, at
+        item_cover[off[i]:off[i + 1]], empty for a dropped item.  A given
+        item_cover that is too small raises SyzsigError(SYZSIG_ERANGE)."""
+        self._check_dev(item_flags, item_keep, run_off, run_errno, run_exec, cover, run_cover_start, run_cover_len,
+                        item_cover)
+        nitems = item_keep.numel()
+        if run_cover_start.numel() != nitems * runs or run_cover_len.numel() != nitems * runs:
+            raise ValueError("run_cover_start / run_cover_len need nitems * runs entries")
+        if nitems and runs and run_off.numel() != nitems * runs + 1:
+            raise ValueError("run_off needs nitems * runs + 1 entries")
+        if item_cover is None:  # the union is no longer than the lists together
+            item_cover = torch.empty(int(run_cover_len.to(torch.int64).sum().item()), dtype=torch.int32,
+                                     device=self.dev)
+        off = torch.empty(nitems + 1, dtype=torch.int64, device=self.dev)
+        n = ctypes.c_uint64()
+        check(self.L.syzsig_triage_cover_dev(self.eng.h, nitems, int(runs), _p(item_flags), _p(item_keep), _p(run_off),
+                                             _p(run_errno), _p(run_exec), _p(cover), cover.numel(),
+                                             _p(run_cover_start), _p(run_cover_len), _p(off), _p(item_cover),
+                                             item_cover.numel(), ctypes.byref(n)))
+        return off, item_cover[: n.value]
 
     def minimize_pred(self, item_off, elems, prios, item_flags, attempts, run_off, run_sigs, run_prio, run_errno,
                       run_exec):

@@ -236,6 +236,20 @@ class Cover:
         if self._s.is_nil() and h.value:
             self._s._h = h
 
+    def merge_dev(self, raw):
+        """Merge of PCs already on the device (syzsig_cover_merge_dev): `raw` is
+        a contiguous 32-bit device tensor on the engine's GPU, e.g. an item's
+        slice from Device.triage_cover -- corpusCover.Merge(inp.Cover),
+        syz-manager/manager.go:998, without a host copy."""
+        if raw.element_size() != 4 or not raw.is_contiguous():
+            raise ValueError("merge_dev needs a contiguous 32-bit device tensor")
+        e = self._s._e
+        h = ctypes.c_void_p(self._s.handle.value or 0)
+        n = raw.numel()
+        check(e.L.syzsig_cover_merge_dev(e.h, ctypes.byref(h), ctypes.c_void_p(raw.data_ptr() if n else 0), n))
+        if self._s.is_nil() and h.value:
+            self._s._h = h
+
     def Serialize(self):
         """cover.go:20-26: the PCs in unspecified order."""
         return self._s.Serialize().Elems if not self._s.is_nil() else np.empty(0, np.uint32)
