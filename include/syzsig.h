@@ -42,7 +42,7 @@ extern "C" {
 #define SYZSIG_ERANGE (-34)    /* a size limit of this ABI exceeded */
 #define SYZSIG_ECORRUPT (-74)  /* panic("corrupted Serial"), pkg/signal/signal.go:60-62 */
 
-#define SYZSIG_ABI_VERSION 5
+#define SYZSIG_ABI_VERSION 6
 
 typedef struct syzsig_ctx syzsig_ctx;
 typedef struct syzsig_set syzsig_set;
@@ -61,8 +61,9 @@ void* syzsig_ctx_stream(syzsig_ctx* ctx);
 int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
 /* With timing on: device time (ms, HIP events on the context stream) of the
  * kernels of the last syzsig_edge_derive_dev / syzsig_minimize_dev call, or the
- * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev or
- * syzsig_triage_cover_dev call (uploads / first kernel to its last kernel,
+ * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev,
+ * syzsig_triage_cover_dev, syzsig_exec_comps_dev, syzsig_comp_map_dev or
+ * syzsig_shrink_expand_dev call (uploads / first kernel to its last kernel,
  * including the host round trips between). */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
 /* Measurement: a plain device copy of `bytes` (16-B aligned buffers and size)
@@ -432,6 +433,64 @@ int syzsig_ingest_exec_output_dev(syzsig_ctx* ctx, const uint32_t* d_out, uint64
                                   uint64_t* d_call_start, uint32_t* d_call_len, uint8_t* d_call_prio,
                                   int32_t* d_call_errno, uint64_t* d_cover_start, uint32_t* d_cover_len,
                                   int32_t* d_prog_status, uint64_t* n_failed);
+
+/* ---- comparison hints: the executor's comps output, CompMap, shrinkExpand ----
+ * SYZSIG_COMPS_TILE: a segment of at most this many keys (comparison triples,
+ * map pairs, replacers: 3, 2 and 1 u64 words) is sorted in LDS by one
+ * workgroup, 48 KB for the triples; longer ones are tile-sorted and
+ * rank-merged through workspace buffers. */
+#define SYZSIG_COMPS_TILE 2048
+
+/* executor/executor.h:576-593 handle_completion with flag_collect_comps, per
+ * call of a batch.  d_comps holds ncmp KCOV_TRACE_CMP records of four u64
+ * (type, arg1, arg2, pc; executor.h:155-160); call c's are the call_len[c]
+ * records from record call_start[c] on.  Per call: std::sort + std::unique on
+ * (type, arg1, arg2) as full u64 words (:861-875; pc takes no part), then every
+ * survivor that ignore() (executor_linux.cc:221-253, the x86_64 branch included,
+ * out_start = the address of the executor's output_data, kMaxOutput = 16 MB)
+ * does not drop is written as write() does (:823-859): (u32)type, then the low
+ * words of the operands sign-extended from the size (3 words), or lo and hi of
+ * each operand for SIZE8 (5 words).  Call c's words go to d_out[5 *
+ * call_start[c] ..] (d_out holds 5 * ncmp words; words outside the written
+ * ranges are left alone), their number to d_out_words[c] and the number of
+ * records written -- the record's comps_size -- to d_comps_cnt[c].  A call of
+ * more than 65535 records (fail("too many comparisons")) or outside the buffer
+ * is SYZSIG_EINVAL, checked before anything is written. */
+int syzsig_exec_comps_dev(syzsig_ctx* ctx, const uint64_t* d_comps, uint64_t ncmp, const uint64_t* d_call_start,
+                          const uint32_t* d_call_len, uint64_t ncalls, uint64_t out_start, uint32_t* d_out,
+                          uint32_t* d_out_words, uint32_t* d_comps_cnt);
+
+/* pkg/ipc/ipc.go:420-465: a call's comparison records parsed into its
+ * prog.CompMap (CompMap.AddComp, prog/hints.go:43-48).  d_words is a buffer of
+ * nwords u32 -- the output of syzsig_exec_comps_dev, or the executor regions
+ * syzsig_ingest_exec_output_dev indexed (for an executed call: comps_start =
+ * cover_start + cover_len, comps_cnt = d_out[call_start - 1]); call c has
+ * comps_cnt[c] records from word comps_start[c] on, inside the region that ends
+ * at comps_end[c] (NULL: at nwords).  d_status[c] = SYZSIG_INGEST_OK,
+ * SYZSIG_INGEST_ECOMPS or SYZSIG_INGEST_ECOMPTYPE where the Go returns an error;
+ * such a call gets an empty map.  The maps come back as CSR: call c's distinct
+ * (key, value) pairs -- pair i = d_pairs[2 i], d_pairs[2 i + 1] -- sorted
+ * ascending by key, then value (one fixed instance of the map's iteration
+ * order) at pairs d_map_off[c] .. d_map_off[c + 1]; d_map_off has ncalls + 1
+ * entries; *n_out = the total.  If it exceeds cap (the capacity of d_pairs in
+ * pairs) nothing is written: SYZSIG_ERANGE with the needed total in *n_out.
+ * A range outside the buffer or more than 65535 records in a call is
+ * SYZSIG_EINVAL. */
+int syzsig_comp_map_dev(syzsig_ctx* ctx, const uint32_t* d_words, uint64_t nwords, const uint64_t* d_comps_start,
+                        const uint32_t* d_comps_cnt, const uint64_t* d_comps_end, uint64_t ncalls,
+                        int32_t* d_status, uint64_t* d_map_off, uint64_t* d_pairs, uint64_t cap, uint64_t* n_out);
+
+/* prog/hints.go:164-218 shrinkExpand(v, compMap) for nq queries (q_call[q],
+ * q_val[q]) against the maps of syzsig_comp_map_dev (npairs = map_off[ncalls]).
+ * special_ints is a host array (prog/rand.go specialInts, at most 4096 entries;
+ * copied during the call).  Query q's distinct replacers come back sorted
+ * ascending at d_rep[rep_off[q] .. rep_off[q + 1]); rep_off has nq + 1 entries;
+ * *n_out = the total.  If it exceeds cap nothing is written: SYZSIG_ERANGE with
+ * the needed total in *n_out.  A query's call outside the maps is SYZSIG_EINVAL. */
+int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_off, const uint64_t* d_pairs, uint64_t ncalls,
+                             uint64_t npairs, const uint32_t* d_q_call, const uint64_t* d_q_val, uint64_t nq,
+                             const uint64_t* special_ints, uint32_t nspecial, uint64_t* d_rep_off, uint64_t* d_rep,
+                             uint64_t cap, uint64_t* n_out);
 
 /* ---- hash-sharded maxSignal across GPUs (one process per GPU) ----
  * The batch is split by program range over G GPUs (serial order = GPU-major);

@@ -27,6 +27,10 @@ SYZSIG_DEBUG_POLL_FAIL = 4096
 SYZSIG_DEBUG_AGG_IDX64 = 8192
 SYZSIG_COVER_DEDUP = 1
 SYZSIG_COVER_TILE = 4096  # include/syzsig.h: longer segments leave the one-workgroup LDS sort
+SYZSIG_COMPS_TILE = 2048  # the same for the comparison hints' keys (comps.hip)
+SYZSIG_INGEST_OK = 0
+SYZSIG_INGEST_ECOMPS = 8
+SYZSIG_INGEST_ECOMPTYPE = 9
 
 
 class SyzsigError(RuntimeError):
@@ -135,6 +139,10 @@ SIGNATURES = {
     "syzsig_edge_cover_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, c_uint32, _P, _P]),
     "syzsig_triage_cover_dev": (c_int, [_P, c_uint64, c_uint32, _P, _P, _P, _P, _P, _P, c_uint64, _P, _P, _P, _P,
                                         c_uint64, POINTER(c_uint64)]),
+    "syzsig_exec_comps_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P, _P]),
+    "syzsig_comp_map_dev": (c_int, [_P, _P, c_uint64, _P, _P, _P, c_uint64, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
+    "syzsig_shrink_expand_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, _P, c_uint64, _P, c_uint32, _P, _P,
+                                         c_uint64, POINTER(c_uint64)]),
     "syzsig_ingest_exec_output_dev": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P, _P, _P, _P,
                                               _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_triage_records_dev": (c_int, [_P, _P, _PP, _P, c_uint64, _P, c_uint32, _P,

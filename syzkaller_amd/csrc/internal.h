@@ -104,7 +104,7 @@ struct syzsig_ctx {
 	// minimize internals and triage pairs (13-15), 16-23 + 30-31 triage aggregation, 55-63 the sharded step and
 	// the LDS records path,
 	// 24-29 check_new_signal uploads, 32-33 the finalize's deferred lists, 40-47 manager poll,
-	// 48-52 the cover sort-unique (cover.hip)
+	// 48-52 the cover sort-unique (cover.hip) and, with 37, the comparison hints' (comps.hip)
 	syz::Workspace ws[64];
 	bool timing = false;                  // HIP events around triage kernels
 	// tuning knobs (defaults; SYZSIG_* environment overrides read at ctx creation)

@@ -146,6 +146,87 @@ class Device:
                                            _lib.SYZSIG_COVER_DEDUP if dedup else 0, _p(cover), _p(cover_cnt)))
         return cover, cover_cnt
 
+    # ---------------------------------------------------------------- comparison hints
+    def _check_cap(self, rc, n):
+        """check(rc); a SYZSIG_ERANGE carries the needed total as .needed"""
+        try:
+            check(rc)
+        except _lib.SyzsigError as e:
+            e.needed = int(n.value)
+            raise
+
+    def exec_comps(self, comps, call_start, call_len, out_start, out=None, out_words=None, comps_cnt=None):
+        """executor.h:576-593 with flag_collect_comps for every call of a batch
+        (syzsig_exec_comps_dev).  comps: int64[ncmp, 4] records (type, arg1,
+        arg2, pc); out_start = the executor's output_data address.  Returns (out
+        int32[5 * ncmp], call c's words at out[5 * call_start[c] : +out_words[c]],
+        out_words int32[ncalls], comps_cnt int32[ncalls] = the records' comps_size)."""
+        self._check_dev(comps, call_start, call_len, out, out_words, comps_cnt)
+        if comps.numel() % 4:
+            raise ValueError("comps holds records of four words")
+        ncmp, ncalls = comps.numel() // 4, call_len.numel()
+        if out is None:
+            out = torch.empty(5 * ncmp, dtype=torch.int32, device=self.dev)
+        if out.numel() < 5 * ncmp:
+            raise ValueError("out needs 5 words per record")
+        if out_words is None:
+            out_words = torch.empty(ncalls, dtype=torch.int32, device=self.dev)
+        if comps_cnt is None:
+            comps_cnt = torch.empty(ncalls, dtype=torch.int32, device=self.dev)
+        check(self.L.syzsig_exec_comps_dev(self.eng.h, _p(comps), ncmp, _p(call_start), _p(call_len), ncalls,
+                                           int(out_start), _p(out), _p(out_words), _p(comps_cnt)))
+        return out, out_words, comps_cnt
+
+    def comp_map(self, words, comps_start, comps_cnt, comps_end=None, pairs=None):
+        """ipc.go:420-465 per call (syzsig_comp_map_dev): comps_cnt[c] records
+        from words[comps_start[c]] on, inside words[:comps_end[c]] (None: the
+        whole buffer).  Returns (status int32[ncalls], map_off int64[ncalls + 1],
+        pairs int64[n, 2]): call c's CompMap as its distinct (key, value) pairs,
+        sorted, at pairs[map_off[c]:map_off[c + 1]].  A given `pairs` that is too
+        small raises SyzsigError(SYZSIG_ERANGE) with the needed pairs in .needed."""
+        self._check_dev(words, comps_start, comps_cnt, comps_end, pairs)
+        ncalls = comps_cnt.numel()
+        if comps_start.numel() != ncalls or (comps_end is not None and comps_end.numel() != ncalls):
+            raise ValueError("comps_start / comps_end need one entry per call")
+        status = torch.empty(ncalls, dtype=torch.int32, device=self.dev)
+        off = torch.empty(ncalls + 1, dtype=torch.int64, device=self.dev)
+        n = ctypes.c_uint64()
+        if pairs is None:  # a record adds two pairs at most
+            pairs = torch.empty((2 * int(comps_cnt.to(torch.int64).sum().item()), 2), dtype=torch.int64,
+                                device=self.dev)
+        self._check_cap(self.L.syzsig_comp_map_dev(self.eng.h, _p(words), words.numel(), _p(comps_start),
+                                                   _p(comps_cnt), _p(comps_end), ncalls, _p(status), _p(off),
+                                                   _p(pairs), pairs.numel() // 2, ctypes.byref(n)), n)
+        return status, off, pairs.view(-1, 2)[: n.value]
+
+    def shrink_expand(self, map_off, pairs, calls, values, special_ints=(), rep=None):
+        """prog/hints.go:164-218 for queries (calls[q], values[q]) against the
+        maps of comp_map (syzsig_shrink_expand_dev).  calls int32[nq], values
+        int64[nq]; special_ints: prog/rand.go's list.  Returns (rep_off
+        int64[nq + 1], rep int64[total]): query q's distinct replacers, sorted
+        as unsigned, at rep[rep_off[q]:rep_off[q + 1]]."""
+        self._check_dev(map_off, pairs, calls, values, rep)
+        nq = calls.numel()
+        if values.numel() != nq:
+            raise ValueError("calls and values need one entry per query")
+        sp = [int(x) & 0xFFFFFFFFFFFFFFFF for x in special_ints]
+        csp = (ctypes.c_uint64 * max(len(sp), 1))(*sp)
+        off = torch.empty(nq + 1, dtype=torch.int64, device=self.dev)
+        n = ctypes.c_uint64()
+
+        def run(r):
+            return self.L.syzsig_shrink_expand_dev(self.eng.h, _p(map_off), _p(pairs), map_off.numel() - 1,
+                                                   pairs.numel() // 2, _p(calls), _p(values), nq, csp, len(sp),
+                                                   _p(off), _p(r), 0 if r is None else r.numel(), ctypes.byref(n))
+        rc = run(rep)
+        if rep is None and rc == _lib.SYZSIG_ERANGE:
+            rep = torch.empty(n.value, dtype=torch.int64, device=self.dev)
+            rc = run(rep)
+        self._check_cap(rc, n)
+        if rep is None:
+            rep = torch.empty(0, dtype=torch.int64, device=self.dev)
+        return off, rep[: n.value]
+
     # ---------------------------------------------------------------- executor output ingest
     def ingest_exec_output(self, out, prog_off, prog_call, call_any, call_num=None, want_cover=False):
         """pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output
