@@ -196,26 +196,65 @@ def minimize(off, elems, prios):
     return [int(x) for x in out[:k]]
 
 
-def run_reference_executor(programs, raw=False):
-    """Run the REFERENCE executor's signal code (oracle/_ref/ref_harness, built
-    from /root/reference by oracle/Makefile) on programs = [[(failed, pcs u64[]), ...], ...].
-    Returns per program (completed, [(call_index, errno, sigs u32[]), ...]), or with raw=True the program's
-    output region words as the executor wrote them (executor.h:566-604)."""
+REF_MODES = {"signal": 0, "cover": 1, "comps": 2}
+REF_PROTOCOL = 0x32485a53  # ref_harness.cc kProtocol
+REF_SOURCE = os.environ.get("REF", "/root/reference")
+
+
+def _run_ref_harness(data):
+    """The harness's output for `data`, past its protocol word.  A binary built from another version of
+    ref_harness.cc (oracle/_ref is not tracked, so one can outlive a checkout) does not answer with the word: it
+    is rebuilt once where the reference is present, and refused otherwise."""
     import struct
 
-    data = [struct.pack("<I", len(programs))]
+    for attempt in (0, 1):
+        r = subprocess.run([REF_HARNESS], input=data, capture_output=True)
+        if r.returncode == 0 and len(r.stdout) >= 12 and struct.unpack_from("<I", r.stdout, 0)[0] == REF_PROTOCOL:
+            return r.stdout[4:]
+        if r.returncode == 4:
+            raise RuntimeError("reference harness: the output region's address was not granted")
+        if attempt == 0 and os.path.isdir(os.path.join(REF_SOURCE, "executor")):
+            subprocess.run(["make", "-s", "-C", HERE, "ref", "REF=" + REF_SOURCE], check=True)
+            continue
+        raise RuntimeError(f"oracle/_ref/ref_harness does not speak this protocol (exit status {r.returncode}): "
+                           "rebuild it with `make -C oracle ref`")
+
+
+def run_reference_executor(programs, raw=False, mode="signal", dedup=True, out_addr=0, info=False):
+    """Run the REFERENCE executor's per-call output code (oracle/_ref/ref_harness, built from /root/reference by
+    oracle/Makefile) on programs = [[(failed, data), ...], ...].
+      mode="signal": data = pcs u64[]; flag_collect_cover and flag_collect_comps off.
+                     Per program (completed, [(call_index, errno, sigs u32[]), ...]).
+      mode="cover":  the same input with flag_collect_cover on and flag_dedup_cover = dedup.
+                     Per program (completed, [(call_index, errno, sigs u32[], cover u32[]), ...]).
+      mode="comps":  data = u64[n, 4] records (type, arg1, arg2, pc); flag_collect_comps on.
+                     Per program (completed, [(call_index, errno, comps words u32[], comps_size), ...]).
+    raw=True gives the program's output region words as the executor wrote them (executor.h:566-604) instead.
+    out_addr != 0 maps the output region there (kcov_comparison_t::ignore reads its address); the harness exits
+    non-zero if the address is not granted.  With info=True the result is (that list, {"out_start": the region's
+    address, "status": every program's child exit status}); without it a child that exits non-zero (a fail() in
+    the reference exits with kFailStatus = 67) raises RuntimeError."""
+    import struct
+
+    per = 4 if mode == "comps" else 1
+    data = [struct.pack("<IIIQI", REF_PROTOCOL, REF_MODES[mode], int(bool(dedup)), int(out_addr), len(programs))]
     for prog in programs:
         data.append(struct.pack("<I", len(prog)))
-        for failed, pcs in prog:
-            pcs = np.ascontiguousarray(pcs, np.uint64)
-            data.append(struct.pack("<II", int(failed), pcs.size))
-            data.append(pcs.tobytes())
-    out = subprocess.run([REF_HARNESS], input=b"".join(data), capture_output=True, check=True).stdout
-    res, pos = [], 0
+        for failed, d in prog:
+            d = np.ascontiguousarray(d, np.uint64)
+            assert d.size % per == 0
+            data.append(struct.pack("<II", int(failed), d.size // per))
+            data.append(d.tobytes())
+    out = _run_ref_harness(b"".join(data))
+    (out_start,) = struct.unpack_from("<Q", out, 0)
+    res, status, pos = [], [], 8
     for _ in programs:
-        (nw,) = struct.unpack_from("<I", out, pos)
-        words = np.frombuffer(out, np.uint32, nw, pos + 4)
-        pos += 4 + 4 * nw
+        st, nw = struct.unpack_from("<II", out, pos)
+        words = np.frombuffer(out, np.uint32, nw, pos + 8)
+        pos += 8 + 4 * nw
+        status.append(st)
+        if st != 0 and not info:
+            raise RuntimeError(f"reference executor child exited with status {st}")
         if raw:
             res.append(words.copy())
             continue
@@ -223,10 +262,23 @@ def run_reference_executor(programs, raw=False):
         calls, q = [], 1
         for _ in range(completed):
             idx, num, err, fault, nsig, ncover, ncomps = (int(x) for x in words[q: q + 7])
-            calls.append((idx, err, np.array(words[q + 7: q + 7 + nsig], np.uint32)))
-            q += 7 + nsig + ncover
+            sigs = np.array(words[q + 7: q + 7 + nsig], np.uint32)
+            q += 7 + nsig
+            cover = np.array(words[q: q + ncover], np.uint32)
+            q += ncover
+            c0 = q
+            for _k in range(ncomps):  # executor.h:848-858: 3 or 5 words by the type's size bits
+                q += 5 if (int(words[q]) & 6) == 6 else 3
+            if mode == "signal":
+                calls.append((idx, err, sigs))
+            elif mode == "cover":
+                calls.append((idx, err, sigs, cover))
+            else:
+                calls.append((idx, err, np.array(words[c0:q], np.uint32), ncomps))
+        assert q == nw
         res.append((completed, calls))
-    return res
+    assert pos == len(out)
+    return (res, {"out_start": out_start, "status": status}) if info else res
 
 
 def triage_batch_into(ms, sigs, call_start, call_len, call_prio, ns=None):

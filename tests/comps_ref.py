@@ -2,11 +2,18 @@
 checker of syzsig_exec_comps_dev, syzsig_comp_map_dev and
 syzsig_shrink_expand_dev.
 
-The compiled reference harness runs with flag_collect_comps off and there is
-no Go toolchain, so this half is pinned by restatement only (DESIGN.md 2:
-partially pinned); tests/test_comps_ref_cpu.py holds this file to hand-derived
-cases.  Plain Python integers throughout: every step is written as the
-reference writes it, one record at a time.
+ignore, write_comp, call_comps / exec_comps and MAX_COMPS are pinned to the
+compiled reference: the harness (oracle/ref_harness.cc, comps mode) runs the
+reference's own handle_completion with flag_collect_comps on, its output
+region mapped at a given address, and tests/test_golden_cover_comps_cpu.py
+holds this file word for word to what it wrote (tests/golden/comps, and a
+live run on fresh records where the harness is built); parse_comps is run on
+the regions the reference wrote, which pins the framing it reads.  What
+parse_comps makes of the records, swap_int and shrink_expand restate Go
+(ipc.go, mutation.go, hints.go; no Go toolchain) and stay restatement-only:
+tests/test_comps_ref_cpu.py holds them to hand-derived cases.  Plain Python
+integers throughout: every step is written as the reference writes it, one
+record at a time.
 
   ignore                executor/executor_linux.cc:221-253
   write_comp            executor/executor.h:823-859

@@ -1,10 +1,14 @@
 """Restatement of the cover half of the per-execution path, the checker of
 syzsig_edge_cover_dev and syzsig_triage_cover_dev.
 
-The compiled reference harness runs with flag_collect_cover off, so this half
-is pinned by restatement only (partially pinned); the reference
-leaves no freedom here (std::sort + std::unique + truncation, and a map
-union), and tests/test_cover_ref_cpu.py holds this file to hand-derived cases.
+call_cover / edge_cover are pinned to the compiled reference: the harness
+(oracle/ref_harness.cc, cover mode) runs the reference's own
+write_coverage_signal with flag_collect_cover on, both values of
+flag_dedup_cover, and tests/test_golden_cover_comps_cpu.py holds this file
+word for word to what it wrote (tests/golden/cover, and a live run on fresh
+traces where the harness is built).  triage_cover restates Go (proc.go, no Go
+toolchain) and stays restatement-only; tests/test_cover_ref_cpu.py holds it to
+hand-derived cases.
 
   call_cover / edge_cover   executor/executor.h:514-527
   triage_cover              syz-fuzzer/proc.go:119-139 and :173
