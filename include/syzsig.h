@@ -42,7 +42,7 @@ extern "C" {
 #define SYZSIG_ERANGE (-34)    /* a size limit of this ABI exceeded */
 #define SYZSIG_ECORRUPT (-74)  /* panic("corrupted Serial"), pkg/signal/signal.go:60-62 */
 
-#define SYZSIG_ABI_VERSION 6
+#define SYZSIG_ABI_VERSION 7
 
 typedef struct syzsig_ctx syzsig_ctx;
 typedef struct syzsig_set syzsig_set;
@@ -64,7 +64,8 @@ int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
  * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev,
  * syzsig_triage_cover_dev, syzsig_exec_comps_dev, syzsig_comp_map_dev or
  * syzsig_shrink_expand_dev call (uploads / first kernel to its last kernel,
- * including the host round trips between). */
+ * including the host round trips between); for syzsig_manager_new_input_batch
+ * the host wall time of the call, which ends synchronised. */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
 /* Measurement: a plain device copy of `bytes` (16-B aligned buffers and size)
  * on the context stream, 16 B per lane per step; *ms = its device time (HIP
@@ -212,6 +213,68 @@ int syzsig_minimize_dev(syzsig_ctx* ctx, const uint64_t* d_ctx_off, const uint32
 int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signal, syzsig_set** new_max, uint32_t nfuzzers,
                               const uint32_t* poll_fuzzer, const uint64_t* poll_off, const uint32_t* elems,
                               const int8_t* prios, uint32_t npolls, syzsig_set** replies);
+
+/* ---- syz-manager/manager.go:976-1025 Manager.NewInput, over a batch of inputs ----
+ * Row i (arrival order) is one RPC's a.RPCInput: its Serial a.Signal =
+ * elems/prios[sig_off[i] .. sig_off[i+1]) (Deserialize rules: a later duplicate
+ * overwrites), its a.Cover = cover[cover_off[i] .. cover_off[i+1]), and
+ * input_key[i] < nkeys a dense index of hash.String(a.Prog) (sha1 stays with
+ * the caller).  The result is the reference's loop over the rows under mgr.mu:
+ *   inputSignal := a.Signal.Deserialize()
+ *   if corpusSignal.Diff(inputSignal).Empty() return          (:993: rejected)
+ *   corpusSignal.Merge(inputSignal); corpusCover.Merge(a.Cover)   (:997-998)
+ *   if the program is in the corpus: its entry's Signal is max-merged with
+ *   inputSignal and its Cover united with a.Cover (:1000-1008), else the input
+ *   becomes the entry (:1009-1022).
+ * An old corpus entry the batch may touch is passed as an ordinary row before
+ * its key's inputs, flagged SYZSIG_INPUT_PRESENT (its stored Signal and Cover):
+ * it takes no part in acceptance and does not go into corpusSignal or
+ * corpusCover; it counts as accepted for its key's merge and makes later rows
+ * of the key "not new".
+ * Outputs (host arrays):
+ *  - accepted[i] = 1 iff row i passed :993 (a PRESENT row: 1);
+ *  - new_key[i] = 1 iff row i is an accepted non-PRESENT row and no earlier
+ *    accepted or PRESENT row has its key (the else branch at :1009: the caller
+ *    saves it and queues it for the other fuzzers);
+ *  - key_touched[k] = 1 iff key k has an accepted non-PRESENT row.  Only such
+ *    keys get CSR ranges: key k's entry Signal -- the max-merge of the
+ *    Deserialized Signals of its PRESENT and accepted rows -- at
+ *    key_elems/key_prios[key_sig_off[k] .. key_sig_off[k+1]), elements ascending,
+ *    and its Cover, the union of the same rows' covers, at
+ *    key_cover[key_cover_off[k] .. key_cover_off[k+1]), PCs ascending and
+ *    distinct (one fixed instance of Serialize's map order; the old entry keeps
+ *    its Call and Prog).  Both offset arrays have nkeys + 1 entries.
+ * *corpus_signal / *corpus_cover: a NULL one is allocated by the first accepted
+ * input (the cover even when that input's cover is empty, cover.go:9-18); a
+ * batch that accepts nothing leaves NULL sets NULL.
+ * All or nothing: sig_cap below the rows' total entries or cover_cap below
+ * their total PCs is SYZSIG_ERANGE (those totals always suffice), a key >=
+ * nkeys or a non-monotone offset SYZSIG_EINVAL, both checked before anything
+ * is touched; on any error the sets and the output arrays are as they were.
+ * A batch of more than 2^23 non-PRESENT entries, or whose entries crowd one
+ * element partition past 2048 (an element present in thousands of inputs),
+ * takes the reference loop input by input over the set ops for acceptance
+ * (same result, slower).  A key's rows hold fewer than 2^32 entries and fewer
+ * than 2^31 PCs (SYZSIG_ERANGE).
+ * SYZSIG_CORPUS_TILE: a key whose rows hold at most this many entries is
+ * sorted by one workgroup pass in LDS; a longer one is tile-sorted and
+ * rank-merged through workspace buffers (its cover alike past
+ * SYZSIG_COVER_TILE PCs). */
+#define SYZSIG_INPUT_PRESENT 1u
+#define SYZSIG_CORPUS_TILE 2048
+int syzsig_manager_new_input_batch(syzsig_ctx* ctx, syzsig_set** corpus_signal, syzsig_set** corpus_cover,
+                                   uint32_t ninputs, uint32_t nkeys, const uint32_t* input_key,
+                                   const uint8_t* input_flags, const uint64_t* sig_off, const uint32_t* elems,
+                                   const int8_t* prios, const uint64_t* cover_off, const uint32_t* cover,
+                                   uint8_t* accepted, uint8_t* new_key, uint8_t* key_touched, uint64_t* key_sig_off,
+                                   uint32_t* key_elems, int8_t* key_prios, uint64_t sig_cap, uint64_t* key_cover_off,
+                                   uint32_t* key_cover, uint64_t cover_cap);
+/* Which paths the context's last syzsig_manager_new_input_batch took (tests,
+ * tuning; results never depend on them): out[0] = 1 when acceptance ran the
+ * sequential loop, out[1] = keys whose entries exceeded SYZSIG_CORPUS_TILE,
+ * out[2] = the rank-merge passes over them, out[3] = keys whose cover exceeded
+ * SYZSIG_COVER_TILE. */
+int syzsig_new_input_stats(syzsig_ctx* ctx, uint64_t out[4]);
 
 /* Minimize sharded by element (one process per GPU): shard `shard` of
  * `nshards` takes only the entries whose element it owns (owner_of, as the

@@ -28,6 +28,8 @@ SYZSIG_DEBUG_AGG_IDX64 = 8192
 SYZSIG_COVER_DEDUP = 1
 SYZSIG_COVER_TILE = 4096  # include/syzsig.h: longer segments leave the one-workgroup LDS sort
 SYZSIG_COMPS_TILE = 2048  # the same for the comparison hints' keys (comps.hip)
+SYZSIG_CORPUS_TILE = 2048  # the same for a corpus key's entries in the NewInput batch (corpus.hip)
+SYZSIG_INPUT_PRESENT = 1  # a NewInput batch row that is the key's old corpus entry
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
 SYZSIG_INGEST_ECOMPTYPE = 9
@@ -122,6 +124,9 @@ SIGNATURES = {
     "syzsig_intersection": (c_int, [_P, _P, _P, _PP]),
     "syzsig_merge": (c_int, [_P, _PP, _P]),
     "syzsig_manager_poll_batch": (c_int, [_P, _PP, _P, c_uint32, _P, _P, _P, _P, c_uint32, _P]),
+    "syzsig_manager_new_input_batch": (c_int, [_P, _PP, _PP, c_uint32, c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, _P, c_uint64, _P, _P, c_uint64]),
+    "syzsig_new_input_stats": (c_int, [_P, _P]),
     "syzsig_cover_merge": (c_int, [_P, _PP, _P, c_uint64]),
     "syzsig_cover_merge_dev": (c_int, [_P, _PP, _P, c_uint64]),
     "syzsig_triage_runs_dev": (c_int, [_P, _P, c_uint64, _P, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P]),

@@ -103,7 +103,8 @@ struct syzsig_ctx {
 	// small state, 7-10 host uploads of minimize, 11-14 triage partitions and
 	// minimize internals and triage pairs (13-15), 16-23 + 30-31 triage aggregation, 55-63 the sharded step and
 	// the LDS records path,
-	// 24-29 check_new_signal uploads, 32-33 the finalize's deferred lists, 40-47 manager poll,
+	// 24-29 check_new_signal uploads, 32-33 the finalize's deferred lists, 40-47 manager poll and
+	// the NewInput batch's acceptance (corpus.hip; its per-key merge: 24-29, 34, 36, 38, 53, 54),
 	// 48-52 the cover sort-unique (cover.hip) and, with 37, the comparison hints' (comps.hip)
 	syz::Workspace ws[64];
 	bool timing = false;                  // HIP events around triage kernels
@@ -129,6 +130,7 @@ struct syzsig_ctx {
 	uint64_t step_src_parts = 1;           // the source run's aggregation partitions
 	bool step_own_timed = false, step_src_timed = false, step_back_timed = false;
 	hipEvent_t ev_step[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	uint64_t ni_stats[4] = {0, 0, 0, 0};  // syzsig_new_input_stats: the last NewInput batch's paths (corpus.hip)
 };
 
 struct syzsig_set {

@@ -21,7 +21,7 @@ from . import _lib
 from ._lib import check
 
 __all__ = ["Engine", "engine", "Signal", "Cover", "Serial", "Context", "FromRaw", "Minimize", "signal_prio",
-           "check_new_signal", "manager_poll"]
+           "check_new_signal", "manager_poll", "manager_new_input", "new_input_stats"]
 
 
 class Engine:
@@ -445,3 +445,71 @@ def manager_poll(max_signal, new_max, polls, eng=None):
             s._h = ctypes.c_void_p(nm[g]) if nm[g] else None
     reps = [Signal(ctypes.c_void_p(rep[i]) if rep[i] else None, eng) for i in range(K)]
     return serialize_many(reps, eng)
+
+
+def manager_new_input(corpus_signal, corpus_cover, rows, nkeys, eng=None):
+    """syz-manager/manager.go:976-1025 Manager.NewInput for a batch of inputs,
+    in arrival order (syzsig_manager_new_input_batch).
+
+    rows = [(key, Serial a.Signal, a.Cover u32[], present)]: key < nkeys is a
+    dense index of hash.String(a.Prog); present (optional, default False)
+    marks the key's old corpus entry, passed before the key's inputs (its
+    stored Signal and Cover).  corpus_signal (a Signal) and corpus_cover (a
+    Cover) are merged in place; nil ones are allocated by the first accepted
+    input.  Returns (accepted, new_key, entries): two uint8 arrays over the
+    rows -- accepted[i]: row i passed corpusSignal.Diff (:993); new_key[i]: it
+    becomes a new corpus entry (:1009) -- and entries = {key: (Serial, cover)}
+    for every key with an accepted input: the entry's Signal (elements
+    ascending) and Cover (PCs ascending) after :1000-1008; the old entry keeps
+    its Call and Prog."""
+    eng = eng or corpus_signal._e
+    K = len(rows)
+    rows = [tuple(r) + (False,) * (4 - len(r)) for r in rows]
+    sers = [(np.ascontiguousarray(s.Elems, np.uint32), np.ascontiguousarray(s.Prios, np.int8)) for _, s, _, _ in rows]
+    for e, p in sers:
+        if e.size != p.size:
+            raise _lib.CorruptedSerial(_lib.SYZSIG_ECORRUPT, "corrupted Serial")  # signal.go:60-62
+    covs = [np.ascontiguousarray(c, np.uint32).ravel() for _, _, c, _ in rows]
+    keys = np.array([int(r[0]) for r in rows], dtype=np.uint32)
+    flags = np.array([_lib.SYZSIG_INPUT_PRESENT if r[3] else 0 for r in rows], dtype=np.uint8)
+    sig_off = np.zeros(K + 1, dtype=np.uint64)
+    np.cumsum(np.array([e.size for e, _ in sers], dtype=np.uint64), out=sig_off[1:])
+    cov_off = np.zeros(K + 1, dtype=np.uint64)
+    np.cumsum(np.array([c.size for c in covs], dtype=np.uint64), out=cov_off[1:])
+    n, c = int(sig_off[-1]), int(cov_off[-1])
+    elems = np.concatenate([e for e, _ in sers]) if n else np.empty(0, np.uint32)
+    prios = np.concatenate([p for _, p in sers]) if n else np.empty(0, np.int8)
+    cover = np.concatenate(covs) if c else np.empty(0, np.uint32)
+    accepted = np.zeros(K, dtype=np.uint8)
+    new_key = np.zeros(K, dtype=np.uint8)
+    touched = np.zeros(nkeys, dtype=np.uint8)
+    k_sig_off = np.zeros(nkeys + 1, dtype=np.uint64)
+    k_cov_off = np.zeros(nkeys + 1, dtype=np.uint64)
+    k_elems, k_prios, k_cover = np.empty(n, np.uint32), np.empty(n, np.int8), np.empty(c, np.uint32)
+    sh = ctypes.c_void_p(corpus_signal.handle.value or 0)
+    ch = ctypes.c_void_p(corpus_cover._s.handle.value or 0)
+    try:
+        check(eng.L.syzsig_manager_new_input_batch(
+            eng.h, ctypes.byref(sh), ctypes.byref(ch), K, int(nkeys), _ptr(keys), _ptr(flags), _ptr(sig_off),
+            _ptr(elems), _ptr(prios), _ptr(cov_off), _ptr(cover), _ptr(accepted), _ptr(new_key), _ptr(touched),
+            _ptr(k_sig_off), _ptr(k_elems), _ptr(k_prios), n, _ptr(k_cov_off), _ptr(k_cover), c))
+    finally:
+        # the library allocates a nil set only on success and leaves the handles as they were on an error
+        if sh.value and corpus_signal.is_nil():
+            corpus_signal._h = sh
+        if ch.value and corpus_cover._s.is_nil():
+            corpus_cover._s._h = ch
+    so, co = k_sig_off.tolist(), k_cov_off.tolist()
+    entries = {int(k): (Serial(k_elems[so[k]:so[k + 1]], k_prios[so[k]:so[k + 1]]), k_cover[co[k]:co[k + 1]])
+               for k in np.flatnonzero(touched).tolist()}
+    return accepted, new_key, entries
+
+
+def new_input_stats(eng=None):
+    """Which paths the engine's last manager_new_input took
+    (syzsig_new_input_stats): sequential acceptance, keys past
+    SYZSIG_CORPUS_TILE entries, merge passes, keys past SYZSIG_COVER_TILE PCs."""
+    eng = eng or engine()
+    out = np.zeros(4, dtype=np.uint64)
+    check(eng.L.syzsig_new_input_stats(eng.h, _ptr(out)))
+    return dict(zip(("sequential", "large_keys", "merge_passes", "large_covers"), (int(x) for x in out)))
