@@ -44,6 +44,7 @@
 //   k_pairs_mark (optional) per-record new bits from the pairs.
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "internal.h"
@@ -2118,7 +2119,8 @@ __global__ __launch_bounds__(256) void k_fin_deferred(const uint32_t* __restrict
 }
 
 // ---------------------------------------------------------------- one-sync run
-// The arguments of the finalize of a one-sync triage run (agg_triage_fused).
+// The arguments of the slice-exclusive finalize and its deferred lists
+// (fin_args fills them, fin_launch hands them to the kernels).
 // (Round 3 measured aggregation and finalize in one launch -- the distinct
 // elements kept in registers, the freed LDS as claim set -- at 1.18 ms against
 // 0.64 + 0.27 for the two launches at C2, and removed it: one 1024-thread
@@ -2141,7 +2143,6 @@ struct FinArgs {
 	unsigned long long* def_cnt;
 	uint64_t* def_ns;
 	unsigned long long* def_ns_cnt;
-	const uint32_t* spill;
 	uint32_t dbg;
 };
 
@@ -2352,6 +2353,121 @@ static uint32_t agg_group_size(uint64_t ncells)
 	return gz;
 }
 
+// The distinct lists and region counts of a run of P partitions.
+static int agg_lists(syzsig_ctx* ctx, uint32_t P, void** de, void** df, void** dc)
+{
+	SYZ_TRY(ws_get(ctx, kWsAggDistE, (uint64_t)P * kAggRegion * 4 + 64, de));
+	SYZ_TRY(ws_get(ctx, kWsAggDistF, (uint64_t)P * kAggRegion * 16 + 64, df));
+	return ws_get(ctx, kWsAggCnt, (uint64_t)(P + 1) * 4 + 64, dc);
+}
+
+// ---- the capped-cell front end: layout, plan, scatter and k_agg of one run,
+// shared by agg_capped, the one-sync run (agg_triage_fused) and the sharded
+// step's fast path (syzsig_step_send_dev).
+struct CapRun {
+	uint64_t nchunks;  // work items
+	uint32_t S;        // cells per work item (= partitions)
+	float sd;          // the cells' slack, in standard deviations
+	uint64_t bound;    // records reserved for the cells; the dummy lines follow
+	uint32_t* recs;
+	uint64_t *sizes, *cbase;              // per work item: records, first record of its cells
+	uint32_t *ccap, *ccnt, *ovf, *tiles;  // cell capacity, records per cell, the spill flag, k_scat3 tiles
+	void *de, *df, *dc;                   // k_agg's output (agg_lists)
+};
+
+// Workspaces of a run's capped cells: the records, then kWsAggCells carved in
+// one fixed layout.
+static int cap_layout(syzsig_ctx* ctx, uint64_t run_recs, uint64_t nchunks, uint32_t S, float sd, CapRun* r)
+{
+	r->nchunks = nchunks;
+	r->S = S;
+	r->sd = sd;
+	// upper bound of sum_c S * cap[c] (k_cell_plan): 1.25 records + per cell
+	// sd^2 + 128; a multiple of 64 records, because the dummy lines after it
+	// take 16-B stores
+	r->bound = (run_recs + run_recs / 4 + nchunks * S * (uint64_t)(sd * sd + 128.0f) + 127) & ~63ull;
+	void *recs, *cm;
+	SYZ_TRY(ws_get(ctx, kWsAggRecs, (r->bound + kDummyLines * kBlk) * 4, &recs));
+	SYZ_TRY(ws_get(ctx, kWsAggCells, nchunks * 24 + (uint64_t)S * nchunks * 4 + 256, &cm));
+	r->recs = (uint32_t*)recs;
+	r->sizes = (uint64_t*)cm;
+	r->cbase = r->sizes + nchunks;
+	r->ccap = (uint32_t*)(r->cbase + nchunks);
+	r->ccnt = r->ccap + nchunks;
+	r->ovf = r->ccnt + (uint64_t)S * nchunks;
+	r->tiles = r->ovf + 1;
+	return agg_lists(ctx, S, &r->de, &r->df, &r->dc);
+}
+
+// The two launches before the scatter.  fast_ctr == nullptr: the planned pair
+// (the caller validated the batch; `tile` = records per k_scat3 tile).  Else
+// the fast pair, which checks the run's assumptions against lm and b->nrec,
+// zeroes b->call_new and the counter block fast_ctr (npairs0 preset) and keeps
+// the run's void flag there: r->ovf becomes the low word of fast_ctr[kCntSpill].
+static int cap_plan(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t c1, const LevelMap& lm,
+                    const AggGeom& g, uint64_t run_recs, CapRun* r, uint32_t tile, unsigned long long* fast_ctr = nullptr,
+                    uint64_t npairs0 = 0)
+{
+	const hipStream_t s = ctx->stream;
+	if (fast_ctr) {
+		void* dpart;
+		SYZ_TRY(ws_get(ctx, kWsFastPart, r->nchunks * 16 + 64, &dpart));
+		r->ovf = (uint32_t*)&fast_ctr[kCntSpill];
+		k_fast_prep<<<(uint32_t)r->nchunks, 256, 0, s>>>(b->call_start, b->call_len, b->call_prio, c0, c1, g.ibits,
+		                                                 b->nrec, r->sizes, (uint64_t*)dpart, b->call_new, lm, r->tiles);
+		k_cell_plan_fast<<<1, 1024, 0, s>>>(r->sizes, r->nchunks, r->S, r->sd, r->cbase, r->ccap,
+		                                    (const uint64_t*)dpart, run_recs, npairs0, fast_ctr);
+	} else {
+		const bool tight = ctx->agg_dbg & SYZSIG_DEBUG_CAP_SPILL;
+		SYZ_HIP(hipMemsetAsync(r->ovf, 0, 4, s));
+		k_chunk_sizes<<<(uint32_t)r->nchunks, 256, 0, s>>>(b->call_len, c0, c1, g.ibits, r->sizes, r->tiles, tile);
+		k_cell_plan<<<1, 1024, 0, s>>>(r->sizes, r->nchunks, r->S, tight ? -1.0f : r->sd, r->cbase, r->ccap);
+	}
+	return SYZSIG_OK;
+}
+
+// Scatter the run's records into its cells, then k_agg.  xp: Minimize's
+// per-record extras (nullptr: a triage run).  ctr: the counter block k_agg
+// reports into and whose void flag (r.ovf) it obeys (nullptr: neither).
+// ev: the context's timing events to record after each of the two (or nullptr).
+static int cap_scatter_agg(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t c1, const LevelMap& lm,
+                           const AggGeom& g, const CapRun& r, uint32_t tile, const AggSrc* xp, unsigned long long* ctr,
+                           hipEvent_t* ev)
+{
+	const hipStream_t s = ctx->stream;
+	const CapCells cc{r.cbase, r.ccap, r.ccnt, r.ovf, r.nchunks, r.recs + r.bound, r.sizes, r.tiles, false, tile};
+	const int pg = (int)std::min<uint64_t>(r.nchunks, 2048);
+	if (xp && SYZ_SCAT3_ENTRY && xp->nshards == 1) {
+		// Minimize: the contexts in rank order (Len desc), so the heavy first
+		// work items fill k_scat3's one-call tiles; the split as for triage
+		CapCells c2 = cc;
+		c2.split = true;
+		if (g.pbits < kAggMaxBits)
+			k_scat3<kAggThreads, SYZ_SCAT3_KE, 4, true, 32><<<pg, kAggThreads, 0, s>>>(
+			    b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, c2, r.recs, *xp);
+		else
+			k_scat3<kAggThreads, SYZ_SCAT3_KE, 4, true, 16><<<pg, kAggThreads, 0, s>>>(
+			    b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, c2, r.recs, *xp);
+		scatter_blk<true>(pg, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, *xp, c2,
+		                  r.recs, ctx->agg_dbg >> 10);
+	} else if (xp)
+		scatter_blk<true>(pg, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, *xp, cc,
+		                  r.recs, ctx->agg_dbg >> 10);
+	else
+		scatter_triage(r.nchunks, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g,
+		               AggSrc{nullptr, 1, 0, 0}, cc, r.recs, ctx->agg_dbg >> 10);
+	SYZ_HIP(hipGetLastError());
+	if (ev && ctx->timing)
+		SYZ_HIP(hipEventRecord(ev[1], s));
+	const AggCells xc{r.recs, nullptr, nullptr, r.cbase, r.ccap, r.ccnt, r.nchunks, g.items_per_chunk_log2(),
+	                  agg_group_size(r.nchunks), ctr ? r.ovf : nullptr, ctr};
+	launch_agg<true>(ctx, r.bound, r.S, s, xc, g, r.de, r.df, r.dc);
+	SYZ_HIP(hipGetLastError());
+	if (ev && ctx->timing)
+		SYZ_HIP(hipEventRecord(ev[2], s));
+	return SYZSIG_OK;
+}
+
 // The count-free attempt: scatter into capped cells (no count pass, no scan),
 // then aggregate.  Cells belong to work items of 2^g.ibits calls (chunks for a
 // triage run, smaller items for Minimize: xp != nullptr).  *done = false when
@@ -2365,67 +2481,21 @@ static int agg_capped(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint6
                       bool* done)
 {
 	*done = false;
-	const AggGeom gs = g;
-	const uint32_t S = 1u << gs.pbits, P = S;
-	const uint64_t nchunks = (c1 - c0 + (1ull << gs.ibits) - 1) >> gs.ibits;  // work items
+	const uint32_t P = 1u << g.pbits;
 	const bool tight = ctx->agg_dbg & SYZSIG_DEBUG_CAP_SPILL;
 	float& slack = xp ? ctx->cap_sd_entry : ctx->cap_sd;
-	const float sd = tight ? 0.0f : slack;
-	// upper bound of sum_c S * cap[c] (k_cell_plan): 1.25 records + per cell sd^2 + 128
-	const uint64_t bound = (run_recs + run_recs / 4 + nchunks * S * (uint64_t)(sd * sd + 128.0f) + 127) & ~63ull;  // (the dummy lines after it: 16-B stores)
-	void *recs, *cm, *de, *df, *dc;
-	SYZ_TRY(ws_get(ctx, 16, (bound + kDummyLines * kBlk) * 4, &recs));
-	SYZ_TRY(ws_get(ctx, 17, nchunks * 24 + (uint64_t)S * nchunks * 4 + 256, &cm));
-	uint64_t* sizes = (uint64_t*)cm;
-	uint64_t* cbase = sizes + nchunks;
-	uint32_t* ccap = (uint32_t*)(cbase + nchunks);
-	uint32_t* ccnt = ccap + nchunks;
-	uint32_t* ovf = ccnt + (uint64_t)S * nchunks;
-	uint32_t* tiles = ovf + 1;
-	SYZ_TRY(ws_get(ctx, 19, (uint64_t)P * kAggRegion * 4 + 64, &de));
-	SYZ_TRY(ws_get(ctx, 20, (uint64_t)P * kAggRegion * 16 + 64, &df));
-	SYZ_TRY(ws_get(ctx, 21, (uint64_t)(P + 1) * 4 + 64, &dc));
+	CapRun r;
+	SYZ_TRY(cap_layout(ctx, run_recs, nchunks_of(c1 - c0, g.ibits), P, tight ? 0.0f : slack, &r));
 	const hipStream_t s = ctx->stream;
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
-	SYZ_HIP(hipMemsetAsync(ovf, 0, 4, s));
 	const uint32_t tile = xp ? kScat3TileEntry : kScat3Tile;
-	k_chunk_sizes<<<(uint32_t)nchunks, 256, 0, s>>>(b->call_len, c0, c1, gs.ibits, sizes, tiles, tile);
-	k_cell_plan<<<1, 1024, 0, s>>>(sizes, nchunks, S, tight ? -1.0f : sd, cbase, ccap);
-	const CapCells cc{cbase, ccap, ccnt, ovf, nchunks, (uint32_t*)recs + bound, sizes, tiles, false, tile};
-	const int pg = (int)std::min<uint64_t>(nchunks, 2048);
-	if (xp && SYZ_SCAT3_ENTRY && xp->nshards == 1) {
-		// Minimize: the contexts in rank order (Len desc), so the heavy first
-		// work items fill k_scat3's one-call tiles; the split as for triage
-		CapCells c2 = cc;
-		c2.split = true;
-		if (gs.pbits < kAggMaxBits)
-			k_scat3<kAggThreads, SYZ_SCAT3_KE, 4, true, 32><<<pg, kAggThreads, 0, s>>>(
-			    b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, gs, c2, (uint32_t*)recs, *xp);
-		else
-			k_scat3<kAggThreads, SYZ_SCAT3_KE, 4, true, 16><<<pg, kAggThreads, 0, s>>>(
-			    b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, gs, c2, (uint32_t*)recs, *xp);
-		scatter_blk<true>(pg, s, gs.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, gs, *xp, c2,
-		                  (uint32_t*)recs, ctx->agg_dbg >> 10);
-	} else if (xp)
-		scatter_blk<true>(pg, s, gs.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0,
-		                                                   c1, gs, *xp, cc, (uint32_t*)recs, ctx->agg_dbg >> 10);
-	else
-		scatter_triage(nchunks_of(c1 - c0, gs.ibits), s, gs.pbits, b->sigs, b->call_start, b->call_len, b->call_prio,
-		               lm, c0, c1, gs, AggSrc{nullptr, 1, 0, 0}, cc, (uint32_t*)recs, ctx->agg_dbg >> 10);
-	SYZ_HIP(hipGetLastError());
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
-	const AggCells xc{(const uint32_t*)recs, nullptr, nullptr, cbase, ccap, ccnt, nchunks, gs.items_per_chunk_log2(),
-	                  agg_group_size(nchunks)};
-	launch_agg<true>(ctx, bound, P, s, xc, gs, de, df, dc);
-	SYZ_HIP(hipGetLastError());
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[2], s));
+	SYZ_TRY(cap_plan(ctx, b, c0, c1, lm, g, run_recs, &r, tile));
+	SYZ_TRY(cap_scatter_agg(ctx, b, c0, c1, lm, g, r, tile, xp, nullptr, ctx->ev));
 	uint32_t* hov = (uint32_t*)(ctx->h_pin + kPinCounts);
 	uint32_t* hcp = hov + 16;
-	SYZ_HIP(hipMemcpyAsync(hcp, dc, P * 4, hipMemcpyDeviceToHost, s));
-	SYZ_HIP(hipMemcpyAsync(hov, ovf, 4, hipMemcpyDeviceToHost, s));
+	SYZ_HIP(hipMemcpyAsync(hcp, r.dc, P * 4, hipMemcpyDeviceToHost, s));
+	SYZ_HIP(hipMemcpyAsync(hov, r.ovf, 4, hipMemcpyDeviceToHost, s));
 	SYZ_HIP(hipStreamSynchronize(s));
 	if (ctx->timing) {
 		float t0 = 0, t1 = 0;
@@ -2453,13 +2523,41 @@ static int agg_capped(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint6
 	st->survivors += D;
 	if (!xp)
 		ctx->agg_distinct_ratio = run_recs ? (double)D / (double)run_recs : 0;
-	out->dist_e = (const uint32_t*)de;
-	out->dist_f = (const uint4*)df;
-	out->cnt = (const uint32_t*)dc;
-	out->nregions = P;
-	out->parts = P;
-	out->D = D;
+	*out = AggOut{(const uint32_t*)r.de, (const uint4*)r.df, (const uint32_t*)r.dc, P, P, D};
 	*done = true;
+	return SYZSIG_OK;
+}
+
+// The HBM fallback for the partitions `ovl` (ovrec records in all) that
+// overflowed the LDS table: launch(ol, gk, gf, C, err) aggregates their cells
+// into the table (gk, gf) of C slots -- k_agg_global or k_agg_global_cap over
+// the device copy ol of ovl, raising *err on an internal error -- and the
+// table's distinct list is compacted to (dist_e, dist_f), which hold at least
+// ovrec entries.  *gcnt = its length, also appended to *rc in pieces of
+// kAggRegion.  Resets the counters; synchronises.
+template <typename Launch>
+static int agg_hbm_fallback(syzsig_ctx* ctx, const std::vector<uint32_t>& ovl, uint64_t ovrec, uint32_t* dist_e,
+                            uint4* dist_f, Launch launch, uint64_t* gcnt, std::vector<uint32_t>* rc)
+{
+	const hipStream_t s = ctx->stream;
+	const uint64_t C = pow2_at_least(std::max<uint64_t>(2 * ovrec, 1024));
+	void *gk, *ol;
+	SYZ_TRY(ws_get(ctx, kWsAggHbmTable, C * 4 + (C + 1) * 16 + 64, &gk));
+	uint32_t* gf = (uint32_t*)((char*)gk + C * 4);
+	SYZ_TRY(ws_get(ctx, kWsAggOvfList, ovl.size() * 4 + 64, &ol));
+	SYZ_HIP(hipMemsetAsync(gk, 0xff, C * 4 + (C + 1) * 16, s));
+	SYZ_HIP(hipMemcpyAsync(ol, ovl.data(), ovl.size() * 4, hipMemcpyHostToDevice, s));
+	SYZ_TRY(counters_reset(ctx));
+	launch((const uint32_t*)ol, (uint32_t*)gk, gf, C, &ctx->d_cnt[kCntError]);
+	k_agg_global_compact<<<grid_for(C + 1, 256, 8192), 256, 0, s>>>((const uint32_t*)gk, gf, C, dist_e, dist_f,
+	                                                                 &ctx->d_cnt[kCntAux2]);
+	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(counters_fetch(ctx));
+	if (ctx->h_cnt[kCntError])
+		return fail(SYZSIG_EIO, "triage: aggregation table overflow (internal error)");
+	*gcnt = ctx->h_cnt[kCntAux2];
+	for (uint64_t left = *gcnt; left; left -= std::min<uint64_t>(left, kAggRegion))
+		rc->push_back((uint32_t)std::min<uint64_t>(left, kAggRegion));
 	return SYZSIG_OK;
 }
 
@@ -2497,9 +2595,9 @@ int agg_aggregate(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t 
 	const uint32_t ilog = g.items_per_chunk_log2();
 	const uint64_t nitems = (c1 - c0 + (1ull << g.ibits) - 1) >> g.ibits;
 	void *recs, *cm, *pm, *de, *df, *dc;
-	SYZ_TRY(ws_get(ctx, 16, run_recs * 4 + 64, &recs));
-	SYZ_TRY(ws_get(ctx, 17, (2 * nitems * P + (uint64_t)P * (nchunks + 1)) * 4 + 64, &cm));
-	SYZ_TRY(ws_get(ctx, 18, (kAggMaxParts + 1) * 8 * 2, &pm));
+	SYZ_TRY(ws_get(ctx, kWsAggRecs, run_recs * 4 + 64, &recs));
+	SYZ_TRY(ws_get(ctx, kWsAggCells, (2 * nitems * P + (uint64_t)P * (nchunks + 1)) * 4 + 64, &cm));
+	SYZ_TRY(ws_get(ctx, kWsAggTotals, (kAggMaxParts + 1) * 8 * 2, &pm));
 	uint32_t* counts = (uint32_t*)cm;
 	uint32_t* offs = counts + nitems * P;
 	uint32_t* offsT = offs + nitems * P;
@@ -2525,9 +2623,7 @@ int agg_aggregate(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t 
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
 	// aggregation
-	SYZ_TRY(ws_get(ctx, 19, (uint64_t)P * kAggRegion * 4 + 64, &de));
-	SYZ_TRY(ws_get(ctx, 20, (uint64_t)P * kAggRegion * 16 + 64, &df));
-	SYZ_TRY(ws_get(ctx, 21, (uint64_t)(P + 1) * 4 + 64, &dc));
+	SYZ_TRY(agg_lists(ctx, P, &de, &df, &dc));
 	const AggCells xc{(const uint32_t*)recs, rec_base, offsT, nullptr, nullptr, nullptr, nchunks, 0,
 	                  agg_group_size(nchunks)};
 	launch_agg<false>(ctx, run_recs, P, s, xc, g, de, df, dc);
@@ -2565,46 +2661,31 @@ int agg_aggregate(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t 
 	if (!ovl.empty()) {
 		// fallback: HBM aggregation table for the overflowed partitions; their
 		// distinct list is appended as extra regions after the P LDS regions
-		const uint64_t C = pow2_at_least(std::max<uint64_t>(2 * ovrec, 1024));
 		const uint64_t extra_regions = (ovrec + kAggRegion - 1) / kAggRegion + 1;
-		void *gk, *gf, *ol;
-		SYZ_TRY(ws_get(ctx, 23, C * 4 + (C + 1) * 16 + 64, &gk));
-		gf = (char*)gk + C * 4;
-		SYZ_TRY(ws_get(ctx, 22, ovl.size() * 4 + 64, &ol));
-		// distinct lists must be contiguous with the regions: grow 19/20 keeping the LDS part
+		// distinct lists must be contiguous with the regions: a bigger pair, the LDS part copied in front
 		const uint64_t tot_e = ((uint64_t)P + extra_regions) * kAggRegion;
 		void *de2, *df2;
-		SYZ_TRY(ws_get(ctx, 30, tot_e * 4 + 64, &de2));
-		SYZ_TRY(ws_get(ctx, 31, tot_e * 16 + 64, &df2));
+		SYZ_TRY(ws_get(ctx, kWsAggDistE2, tot_e * 4 + 64, &de2));
+		SYZ_TRY(ws_get(ctx, kWsAggDistF2, tot_e * 16 + 64, &df2));
 		SYZ_HIP(hipMemcpyAsync(de2, de, (uint64_t)P * kAggRegion * 4, hipMemcpyDeviceToDevice, s));
 		SYZ_HIP(hipMemcpyAsync(df2, df, (uint64_t)P * kAggRegion * 16, hipMemcpyDeviceToDevice, s));
-		SYZ_HIP(hipMemsetAsync(gk, 0xff, C * 4 + (C + 1) * 16, s));
-		SYZ_HIP(hipMemcpyAsync(ol, ovl.data(), ovl.size() * 4, hipMemcpyHostToDevice, s));
-		SYZ_TRY(counters_reset(ctx));
-		const uint64_t items = ovl.size() * ((nchunks + kAggGroup - 1) / kAggGroup);
-		k_agg_global<<<grid_for(items * 64, 256, 8192), 256, 0, s>>>((const uint32_t*)recs, rec_base,
-		                                                              (const uint32_t*)offsT, nchunks, g,
-		                                                              (const uint32_t*)ol, (uint32_t)ovl.size(),
-		                                                              (uint32_t*)gk, (uint32_t*)gf, C,
-		                                                              &ctx->d_cnt[kCntError]);
-		k_agg_global_compact<<<grid_for(C + 1, 256, 8192), 256, 0, s>>>(
-		    (const uint32_t*)gk, (const uint32_t*)gf, C, (uint32_t*)de2 + (uint64_t)P * kAggRegion,
-		    (uint4*)df2 + (uint64_t)P * kAggRegion, &ctx->d_cnt[kCntAux2]);
-		SYZ_HIP(hipGetLastError());
-		SYZ_TRY(counters_fetch(ctx));
-		if (ctx->h_cnt[kCntError])
-			return fail(SYZSIG_EIO, "triage: aggregation table overflow (internal error)");
-		const uint64_t gcnt = ctx->h_cnt[kCntAux2];
-		D += gcnt;
 		// region counts: LDS partitions (overflowed = 0), then the fallback list in kAggRegion pieces
 		std::vector<uint32_t> rc(hc);
 		for (uint32_t p : ovl)
 			rc[p] = 0;
-		for (uint64_t left = gcnt; left; left -= std::min<uint64_t>(left, kAggRegion))
-			rc.push_back((uint32_t)std::min<uint64_t>(left, kAggRegion));
+		const uint64_t items = ovl.size() * ((nchunks + kAggGroup - 1) / kAggGroup);
+		const auto launch = [&](const uint32_t* ol, uint32_t* gk, uint32_t* gf, uint64_t C, unsigned long long* err) {
+			k_agg_global<<<grid_for(items * 64, 256, 8192), 256, 0, s>>>((const uint32_t*)recs, rec_base,
+			                                                              (const uint32_t*)offsT, nchunks, g, ol,
+			                                                              (uint32_t)ovl.size(), gk, gf, C, err);
+		};
+		uint64_t gcnt = 0;
+		SYZ_TRY(agg_hbm_fallback(ctx, ovl, ovrec, (uint32_t*)de2 + (uint64_t)P * kAggRegion,
+		                         (uint4*)df2 + (uint64_t)P * kAggRegion, launch, &gcnt, &rc));
+		D += gcnt;
 		nregions = (uint32_t)rc.size();
 		void* dc2;
-		SYZ_TRY(ws_get(ctx, 21, rc.size() * 4 + 64, &dc2));
+		SYZ_TRY(ws_get(ctx, kWsAggCnt, rc.size() * 4 + 64, &dc2));
 		SYZ_HIP(hipMemcpyAsync(dc2, rc.data(), rc.size() * 4, hipMemcpyHostToDevice, s));
 		SYZ_HIP(hipStreamSynchronize(s));  // rc is a host temporary
 		dc = dc2;
@@ -2617,12 +2698,7 @@ int agg_aggregate(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t 
 	st->survivors += D;
 	if (!entry)
 		ctx->agg_distinct_ratio = run_recs ? (double)D / (double)run_recs : 0;
-	out->dist_e = (const uint32_t*)dist_e;
-	out->dist_f = (const uint4*)dist_f;
-	out->cnt = (const uint32_t*)dc;
-	out->nregions = nregions;
-	out->parts = P;
-	out->D = D;
+	*out = AggOut{(const uint32_t*)dist_e, (const uint4*)dist_f, (const uint32_t*)dc, nregions, P, D};
 	return SYZSIG_OK;
 }
 
@@ -2651,7 +2727,7 @@ static int reserve_slices(syzsig_ctx* ctx, syzsig_set* s, const uint32_t* dist_e
 		return SYZSIG_OK;
 	const uint32_t P = 1u << pbits;
 	void* wh;
-	SYZ_TRY(ws_get(ctx, 53, (uint64_t)P * 4 + 64, &wh));
+	SYZ_TRY(ws_get(ctx, kWsPartHist, (uint64_t)P * 4 + 64, &wh));
 	const hipStream_t st = ctx->stream;
 	SYZ_HIP(hipMemsetAsync(wh, 0, (uint64_t)P * 4, st));
 	k_part_hist<<<std::min<uint32_t>(r1 - r0, 2048), 256, 0, st>>>(dist_e, d_cnt, r0, r1, pbits, (uint32_t*)wh);
@@ -2663,6 +2739,74 @@ static int reserve_slices(syzsig_ctx* ctx, syzsig_set* s, const uint32_t* dist_e
 	const uint64_t need = pow2_at_least((uint64_t)((double)P * (double)mx / (kBucketSlots * kMaxLoad)) + 1);
 	if (need > s->nbuckets)
 		SYZ_TRY(set_rehash(s, need, false));
+	return SYZSIG_OK;
+}
+
+// A newSignal set made for this run (newSignal.Merge allocates a nil receiver,
+// signal.go:121-125 -- but only when some DiffRaw is non-empty): dropped again,
+// *ns back to nil, on every return that does not keep() it.
+struct FreshNs {
+	syzsig_set** ns;
+	bool armed;
+	FreshNs(syzsig_set** p, bool fresh) : ns(p), armed(fresh) {}
+	FreshNs(const FreshNs&) = delete;
+	~FreshNs() { drop(); }
+	void keep() { armed = false; }
+	bool drop()  // true: the set was this run's and is gone
+	{
+		if (armed) {
+			syzsig_set_free(*ns);
+			*ns = nullptr;
+		}
+		return std::exchange(armed, false);
+	}
+};
+
+// Zero the counters, with the pair cursor (kCntAux2) at npairs: the finalize
+// kernels append the run's pairs after the batch's earlier ones.
+static int seed_pair_counter(syzsig_ctx* ctx, uint64_t npairs)
+{
+	SYZ_TRY(counters_reset(ctx));
+	memcpy(ctx->h_pin + kPinPairs, &npairs, 8);  // consumed before the caller's next counters_fetch
+	SYZ_HIP(hipMemcpyAsync(&ctx->d_cnt[kCntAux2], ctx->h_pin + kPinPairs, 8, hipMemcpyHostToDevice, ctx->stream));
+	return SYZSIG_OK;
+}
+
+// The slice-exclusive finalize's arguments for a run of 2^pbits partitions and
+// at most n distinct elements (the deferred lists' capacity): both tables have
+// at least a bucket per partition.
+static int fin_args(syzsig_ctx* ctx, const syzsig_set* ms, const syzsig_set* nsp, uint32_t pbits, const LevelMap& lm,
+                    uint64_t c0, const syzsig_batch* b, uint64_t* pairs, uint64_t n, FinArgs* fa)
+{
+	void *dd, *dn;
+	SYZ_TRY(ws_get(ctx, kWsFinDefer, n * 20 + 64, &dd));
+	SYZ_TRY(ws_get(ctx, kWsFinDeferNs, n * 8 + 64, &dn));
+	*fa = FinArgs{lm, c0, ms->slots, ms->nbuckets - 1, (63 - __builtin_clzll(ms->nbuckets)) - pbits, nsp->slots,
+	              nsp->nbuckets - 1, (63 - __builtin_clzll(nsp->nbuckets)) - pbits, b->call_new, pairs,
+	              &ctx->d_cnt[kCntAux2], ctx->d_cnt, (uint32_t*)dd, (uint4*)((char*)dd + ((n * 4 + 15) & ~15ull)),
+	              &ctx->d_cnt[kCntDefer], (uint64_t*)dn, &ctx->d_cnt[kCntDeferNs], ctx->agg_dbg};
+	return SYZSIG_OK;
+}
+
+// The slice-exclusive finalize over the regions (all partitions), then the
+// deferred lists.  A one-sync run passes its void flag `spill`, the counter of
+// overflowed partitions and the gate past which nothing is committed.
+// (The deferred lists in a launch of their own: taken by the finalize's last
+// block instead, they made the finalize 1.03 ms instead of 0.27 at C2.)
+static int fin_launch(syzsig_ctx* ctx, const FinArgs& fa, const uint32_t* dist_e, const uint4* dist_f,
+                      const uint32_t* cnt, uint32_t nregions, const uint32_t* spill = nullptr,
+                      unsigned long long* agg_ovf = nullptr, uint32_t gate = 0)
+{
+	const hipStream_t s = ctx->stream;
+	k_agg_finalize_x<2><<<nregions, kFxThreads, 0, s>>>(
+	    dist_e, dist_f, cnt, nregions, fa.lm, fa.c0, fa.slots, fa.bmask, fa.ms_shift, fa.ns_slots, fa.ns_bmask,
+	    fa.ns_shift, fa.call_new, fa.pairs, fa.npairs, fa.ctr, fa.def_e, fa.def_f, fa.def_cnt, fa.def_ns, fa.def_ns_cnt,
+	    fa.dbg, spill, agg_ovf, gate);
+	SYZ_HIP(hipGetLastError());
+	k_fin_deferred<<<2 * kDeferBlocks, 256, 0, s>>>(fa.def_e, fa.def_f, fa.def_cnt, fa.lm, fa.c0, fa.slots, fa.bmask,
+	                                                fa.ns_slots, fa.ns_bmask, fa.call_new, fa.pairs, fa.npairs, fa.ctr,
+	                                                fa.def_ns, fa.def_ns_cnt);
+	SYZ_HIP(hipGetLastError());
 	return SYZSIG_OK;
 }
 
@@ -2678,20 +2822,14 @@ static int reserve_slices(syzsig_ctx* ctx, syzsig_set* s, const uint32_t* dist_e
 // counted cells next, the slack doubled).
 static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsig_batch* b, uint64_t c0,
                             uint64_t c1, const LevelMap& lm, uint64_t run_recs, syzsig_batch_stats* st,
-                            uint64_t** pairs_out, uint64_t* npairs_io, bool* done, bool fast = false,
-                            bool* assumed_bad = nullptr, bool* regeom = nullptr)
+                            uint64_t** pairs_out, uint64_t* npairs_io, bool* done, bool fast, bool* assumed_bad,
+                            bool* regeom)
 {
-	*done = false;
-	bool regeom_local = false;
-	if (!regeom)
-		regeom = &regeom_local;
-	*regeom = false;
-	if (assumed_bad)
-		*assumed_bad = false;
+	*done = *regeom = *assumed_bad = false;
 	AggGeom g = agg_geom_for(ctx, run_recs, 0);
 	g.ibits = g.cbits();  // work items are whole chunks
 	const uint32_t S = 1u << g.pbits, P = S;
-	const uint64_t nchunks = (c1 - c0 + (1ull << g.ibits) - 1) >> g.ibits;
+	const uint64_t nchunks = nchunks_of(c1 - c0, g.ibits);
 	// distinct elements the run can commit: an LDS partition holds at
 	// most kAggLimit (one that overflows is committed after the sync)
 	const uint64_t d_max = std::min<uint64_t>(run_recs, (uint64_t)P * kAggLimit);
@@ -2700,125 +2838,53 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 	// capacity for every possible change, before anything is committed
 	SYZ_TRY(set_reserve(ms, d_est));
 	SYZ_TRY(set_reserve_load(ms, d_max, kHardLoad));
-	// newSignal.Merge allocates a nil receiver (signal.go:121-125) -- but only
-	// when some DiffRaw is non-empty: a fresh set is dropped again if nothing changed
-	const bool fresh_ns = !*ns;
-	if (fresh_ns)
+	FreshNs fresh(ns, !*ns);
+	if (fresh.armed)
 		SYZ_TRY(syzsig_set_make(ctx, d_est, ns));
 	syzsig_set* nsp = *ns;
 	// at most half full for the expected changes (short probe chains: 0.34 ->
 	// 0.28 ms at C2), never past kHardLoad for the largest possible count
 	SYZ_TRY(set_reserve_load(nsp, d_est, kTargetLoad));
 	SYZ_TRY(set_reserve_load(nsp, d_max, kHardLoad));
-	if (ms->nbuckets < P || nsp->nbuckets < P) {  // slices need a bucket per partition
-		if (fresh_ns) {
-			syzsig_set_free(nsp);
-			*ns = nullptr;
-		}
+	if (ms->nbuckets < P || nsp->nbuckets < P)  // slices need a bucket per partition
 		return SYZSIG_OK;
-	}
-	const float sd = ctx->cap_sd;
-	const uint64_t bound = (run_recs + run_recs / 4 + nchunks * S * (uint64_t)(sd * sd + 128.0f) + 127) & ~63ull;  // (the dummy lines after it: 16-B stores)
-	void *recs, *cm, *dc, *pr, *dd, *dn;
-	SYZ_TRY(ws_get(ctx, 16, (bound + kDummyLines * kBlk) * 4, &recs));
-	SYZ_TRY(ws_get(ctx, 17, nchunks * 24 + (uint64_t)S * nchunks * 4 + 256, &cm));
-	uint64_t* sizes = (uint64_t*)cm;
-	uint64_t* cbase = sizes + nchunks;
-	uint32_t* ccap = (uint32_t*)(cbase + nchunks);
-	uint32_t* ccnt = ccap + nchunks;
-	uint32_t* ovf = ccnt + (uint64_t)S * nchunks;
-	uint32_t* tiles = ovf + 1;
-	SYZ_TRY(ws_get(ctx, 21, (uint64_t)(P + 1) * 4 + 64, &dc));
+	CapRun r;
+	SYZ_TRY(cap_layout(ctx, run_recs, nchunks, S, ctx->cap_sd, &r));
+	void* pr;
 	if (fast && *npairs_io == 0 && b->new_pairs && b->new_pairs_cap >= 4 * d_max) {
 		pr = b->new_pairs;  // every possible pair fits the caller's buffer: no copy afterwards
 	} else {
-		SYZ_TRY(ws_grow_keep(ctx, 15, (*npairs_io + 4 * d_max) * 8 + 64, *npairs_io * 8, &pr));
+		SYZ_TRY(ws_grow_keep(ctx, kWsPairs, (*npairs_io + 4 * d_max) * 8 + 64, *npairs_io * 8, &pr));
 	}
 	*pairs_out = (uint64_t*)pr;
-	SYZ_TRY(ws_get(ctx, 32, d_max * 20 + 64, &dd));
-	SYZ_TRY(ws_get(ctx, 33, d_max * 8 + 64, &dn));
+	const uint32_t pb = g.pbits;
+	FinArgs fa;
+	SYZ_TRY(fin_args(ctx, ms, nsp, pb, lm, c0, b, (uint64_t*)pr, d_max, &fa));
 	const hipStream_t s = ctx->stream;
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
 	if (fast) {
-		// two launches before the scatter: per-chunk sizes and checks (call_new
-		// zeroed too), then the cell plan, which also zeroes the counters and
-		// sets the run's void flag (ovf = the low word of ctr[kCntSpill])
-		void* dpart;
-		SYZ_TRY(ws_get(ctx, 54, nchunks * 16 + 64, &dpart));
-		ovf = (uint32_t*)&ctx->d_cnt[kCntSpill];
-		k_fast_prep<<<(uint32_t)nchunks, 256, 0, s>>>(b->call_start, b->call_len, b->call_prio, c0, c1, g.ibits, b->nrec,
-		                                              sizes, (uint64_t*)dpart, b->call_new, lm, tiles);
-		k_cell_plan_fast<<<1, 1024, 0, s>>>(sizes, nchunks, S, sd, cbase, ccap, (const uint64_t*)dpart, run_recs,
-		                                    *npairs_io, ctx->d_cnt);
+		// per-chunk sizes and checks (call_new zeroed too), then the cell plan,
+		// which also zeroes the counters and sets the run's void flag
+		SYZ_TRY(cap_plan(ctx, b, c0, c1, lm, g, run_recs, &r, kScat3Tile, ctx->d_cnt, *npairs_io));
 	} else {
-		SYZ_TRY(counters_reset(ctx));
-		memcpy(ctx->h_pin + kPinPairs, npairs_io, 8);  // consumed before the counters_fetch below
-		SYZ_HIP(hipMemcpyAsync(&ctx->d_cnt[kCntAux2], ctx->h_pin + kPinPairs, 8, hipMemcpyHostToDevice, s));
-		SYZ_HIP(hipMemsetAsync(ovf, 0, 4, s));
-		k_chunk_sizes<<<(uint32_t)nchunks, 256, 0, s>>>(b->call_len, c0, c1, g.ibits, sizes, tiles, kScat3Tile);
-		k_cell_plan<<<1, 1024, 0, s>>>(sizes, nchunks, S, sd, cbase, ccap);
+		SYZ_TRY(seed_pair_counter(ctx, *npairs_io));
+		SYZ_TRY(cap_plan(ctx, b, c0, c1, lm, g, run_recs, &r, kScat3Tile));
 	}
-	const CapCells cc{cbase, ccap, ccnt, ovf, nchunks, (uint32_t*)recs + bound, sizes, tiles, false, kScat3Tile};
-	scatter_triage(nchunks, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g,
-	               AggSrc{nullptr, 1, 0, 0}, cc, (uint32_t*)recs, ctx->agg_dbg >> 10);
-	SYZ_HIP(hipGetLastError());
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
-	const uint32_t pb = g.pbits;
-	FinArgs fa;
-	fa.lm = lm;
-	fa.c0 = c0;
-	fa.slots = ms->slots;
-	fa.bmask = ms->nbuckets - 1;
-	fa.ms_shift = (63 - __builtin_clzll(ms->nbuckets)) - pb;
-	fa.ns_slots = nsp->slots;
-	fa.ns_bmask = nsp->nbuckets - 1;
-	fa.ns_shift = (63 - __builtin_clzll(nsp->nbuckets)) - pb;
-	fa.call_new = b->call_new;
-	fa.pairs = (uint64_t*)pr;
-	fa.npairs = &ctx->d_cnt[kCntAux2];
-	fa.ctr = ctx->d_cnt;
-	fa.def_e = (uint32_t*)dd;
-	fa.def_f = (uint4*)((char*)dd + ((d_max * 4 + 15) & ~15ull));
-	fa.def_cnt = &ctx->d_cnt[kCntDefer];
-	fa.def_ns = (uint64_t*)dn;
-	fa.def_ns_cnt = &ctx->d_cnt[kCntDeferNs];
-	fa.spill = ovf;
-	fa.dbg = ctx->agg_dbg;
-	const AggCells xc{(const uint32_t*)recs, nullptr, nullptr, cbase, ccap, ccnt, nchunks, 0, agg_group_size(nchunks),
-	                  ovf, ctx->d_cnt};
+	// k_agg's distinct lists go through HBM (5 M x 20 B at C2) to the
+	// slice-exclusive finalize: a workgroup of the finalize is small, so many
+	// run per CU and their random probes overlap
+	SYZ_TRY(cap_scatter_agg(ctx, b, c0, c1, lm, g, r, kScat3Tile, nullptr, ctx->d_cnt, ctx->ev));
 	// more overflowed partitions than this and the split path commits nothing:
 	// the run is redone with partitions sized from what k_agg counted
 	const uint32_t gate = P / 8;
-	{
-		// k_agg's distinct lists through HBM (5 M x 20 B at C2), then the
-		// slice-exclusive finalize: a workgroup of the finalize is small, so
-		// many run per CU and their random probes overlap
-		void *de, *df;
-		SYZ_TRY(ws_get(ctx, 19, (uint64_t)P * kAggRegion * 4 + 64, &de));
-		SYZ_TRY(ws_get(ctx, 20, (uint64_t)P * kAggRegion * 16 + 64, &df));
-		launch_agg<true>(ctx, bound, P, s, xc, g, de, df, dc);
-		SYZ_HIP(hipGetLastError());
-		if (ctx->timing)
-			SYZ_HIP(hipEventRecord(ctx->ev[2], s));
-		k_agg_finalize_x<2><<<P, kFxThreads, 0, s>>>(
-		    (const uint32_t*)de, (const uint4*)df, (const uint32_t*)dc, P, lm, c0, fa.slots, fa.bmask, fa.ms_shift,
-		    fa.ns_slots, fa.ns_bmask, fa.ns_shift, fa.call_new, fa.pairs, fa.npairs, ctx->d_cnt, fa.def_e, fa.def_f,
-		    fa.def_cnt, fa.def_ns, fa.def_ns_cnt, ctx->agg_dbg, ovf, &ctx->d_cnt[kCntAggOvf], gate);
-		SYZ_HIP(hipGetLastError());
-	}
-	// (the deferred lists in a launch of their own: taken by the finalize's last
-	// block instead, they made the finalize 1.03 ms instead of 0.27 at C2)
-	k_fin_deferred<<<2 * kDeferBlocks, 256, 0, s>>>(fa.def_e, fa.def_f, fa.def_cnt, lm, c0, ms->slots, ms->nbuckets - 1,
-	                                                nsp->slots, nsp->nbuckets - 1, b->call_new, (uint64_t*)pr,
-	                                                fa.npairs, ctx->d_cnt, fa.def_ns, fa.def_ns_cnt);
-	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(fin_launch(ctx, fa, (const uint32_t*)r.de, (const uint4*)r.df, (const uint32_t*)r.dc, P, r.ovf,
+	                   &ctx->d_cnt[kCntAggOvf], gate));
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[3], s));
 	uint32_t* hov = (uint32_t*)(ctx->h_pin + kPinCounts);
 	if (!fast)
-		SYZ_HIP(hipMemcpyAsync(hov, ovf, 4, hipMemcpyDeviceToHost, s));
+		SYZ_HIP(hipMemcpyAsync(hov, r.ovf, 4, hipMemcpyDeviceToHost, s));
 	SYZ_TRY(counters_fetch(ctx));  // the run's one synchronisation
 	if (fast) {
 		*hov = (uint32_t)ctx->h_cnt[kCntSpill];
@@ -2835,19 +2901,11 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 	}
 	if (*hov & 6) {  // an optimistic run's assumptions failed: nothing committed
 		*assumed_bad = true;
-		if (fresh_ns) {
-			syzsig_set_free(nsp);
-			*ns = nullptr;
-		}
 		return SYZSIG_OK;
 	}
 	if (*hov) {  // a cell spilled: nothing committed, redo with counted cells
 		st->retries++;
 		ctx->cap_sd = ctx->cap_sd * 2 > kCapSdMax ? 0.0f : ctx->cap_sd * 2;
-		if (fresh_ns) {
-			syzsig_set_free(nsp);
-			*ns = nullptr;
-		}
 		return SYZSIG_OK;
 	}
 	if (ctx->h_cnt[kCntOverflow])
@@ -2866,10 +2924,6 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 		const double seen = novf * 2 >= P ? (double)run_recs : (double)D + 2.0 * (double)novf * kAggLimit;
 		ctx->agg_distinct_ratio = std::max(ctx->agg_distinct_ratio, seen / (double)std::max<uint64_t>(run_recs, 1));
 		st->retries++;
-		if (fresh_ns) {
-			syzsig_set_free(nsp);
-			*ns = nullptr;
-		}
 		*regeom = true;
 		return SYZSIG_OK;
 	}
@@ -2883,11 +2937,11 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 		inserted_done += inserted;
 		inserted = ns_ins = 0;
 		std::vector<uint32_t> hc(P);
-		SYZ_HIP(hipMemcpy(hc.data(), dc, P * 4, hipMemcpyDeviceToHost));
+		SYZ_HIP(hipMemcpy(hc.data(), r.dc, P * 4, hipMemcpyDeviceToHost));
 		std::vector<uint32_t> ovl;
 		uint64_t ovrec = 0;
 		std::vector<uint32_t> hcnt((uint64_t)P * nchunks);
-		SYZ_HIP(hipMemcpy(hcnt.data(), ccnt, hcnt.size() * 4, hipMemcpyDeviceToHost));
+		SYZ_HIP(hipMemcpy(hcnt.data(), r.ccnt, hcnt.size() * 4, hipMemcpyDeviceToHost));
 		for (uint32_t q = 0; q < P; q++) {
 			if (hc[q] != kAggOverflow)
 				continue;
@@ -2895,58 +2949,42 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 			for (uint64_t c = 0; c < nchunks; c++)
 				ovrec += hcnt[(uint64_t)q * nchunks + c];
 		}
-		const uint64_t C = pow2_at_least(std::max<uint64_t>(2 * ovrec, 1024));
-		void *gk, *ol, *de2, *df2, *dc2;
-		SYZ_TRY(ws_get(ctx, 23, C * 4 + (C + 1) * 16 + 64, &gk));
-		void* gf = (char*)gk + C * 4;
-		SYZ_TRY(ws_get(ctx, 22, ovl.size() * 4 + 64, &ol));
-		SYZ_TRY(ws_get(ctx, 30, ovrec * 4 + 64, &de2));
-		SYZ_TRY(ws_get(ctx, 31, ovrec * 16 + 64, &df2));
-		SYZ_HIP(hipMemsetAsync(gk, 0xff, C * 4 + (C + 1) * 16, s));
-		SYZ_HIP(hipMemcpyAsync(ol, ovl.data(), ovl.size() * 4, hipMemcpyHostToDevice, s));
-		SYZ_TRY(counters_reset(ctx));
-		k_agg_global_cap<<<grid_for(ovl.size() * nchunks * 64, 256, 8192), 256, 0, s>>>(
-		    (const uint32_t*)recs, cbase, ccap, ccnt, nchunks, g, (const uint32_t*)ol, (uint32_t)ovl.size(),
-		    (uint32_t*)gk, (uint32_t*)gf, C, &ctx->d_cnt[kCntError]);
-		k_agg_global_compact<<<grid_for(C + 1, 256, 8192), 256, 0, s>>>((const uint32_t*)gk, (const uint32_t*)gf, C,
-		                                                                 (uint32_t*)de2, (uint4*)df2,
-		                                                                 &ctx->d_cnt[kCntAux2]);
-		SYZ_HIP(hipGetLastError());
-		SYZ_TRY(counters_fetch(ctx));
-		if (ctx->h_cnt[kCntError])
-			return fail(SYZSIG_EIO, "triage: aggregation table overflow (internal error)");
-		const uint64_t gcnt = ctx->h_cnt[kCntAux2];
-		D += gcnt;
+		void *de2, *df2, *dc2;
+		SYZ_TRY(ws_get(ctx, kWsAggDistE2, ovrec * 4 + 64, &de2));
+		SYZ_TRY(ws_get(ctx, kWsAggDistF2, ovrec * 16 + 64, &df2));
+		const auto launch = [&](const uint32_t* ol, uint32_t* gk, uint32_t* gf, uint64_t C, unsigned long long* err) {
+			k_agg_global_cap<<<grid_for(ovl.size() * nchunks * 64, 256, 8192), 256, 0, s>>>(
+			    r.recs, r.cbase, r.ccap, r.ccnt, nchunks, g, ol, (uint32_t)ovl.size(), gk, gf, C, err);
+		};
+		uint64_t gcnt = 0;
 		std::vector<uint32_t> rc;
-		for (uint64_t left = gcnt; left; left -= std::min<uint64_t>(left, kAggRegion))
-			rc.push_back((uint32_t)std::min<uint64_t>(left, kAggRegion));
+		SYZ_TRY(agg_hbm_fallback(ctx, ovl, ovrec, (uint32_t*)de2, (uint4*)df2, launch, &gcnt, &rc));
+		D += gcnt;
 		if (!rc.empty()) {
 			// the reservations above covered the committed partitions (<= kAggLimit
 			// distinct each); these elements come on top
 			SYZ_TRY(set_reserve(ms, gcnt));
 			SYZ_TRY(set_reserve_load(nsp, gcnt, kHardLoad));
-			SYZ_TRY(ws_get(ctx, 35, rc.size() * 4 + 64, &dc2));
+			SYZ_TRY(ws_get(ctx, kWsAggHbmCnt, rc.size() * 4 + 64, &dc2));
 			SYZ_HIP(hipMemcpyAsync(dc2, rc.data(), rc.size() * 4, hipMemcpyHostToDevice, s));
 			SYZ_TRY(reserve_slices(ctx, ms, (const uint32_t*)de2, (const uint32_t*)dc2, 0, (uint32_t)rc.size(), pb));
 			SYZ_TRY(reserve_slices(ctx, nsp, (const uint32_t*)de2, (const uint32_t*)dc2, 0, (uint32_t)rc.size(), pb));
 			if (pr == b->new_pairs) {
 				// the run wrote its pairs straight into the caller's buffer: keep
-				// appending there while it has room, else move them to workspace
-				// 15 first (ws_grow_keep keeps only what that workspace held)
+				// appending there while it has room, else move them to kWsPairs
+				// first (ws_grow_keep keeps only what that workspace held)
 				if (b->new_pairs_cap < npairs + 4 * gcnt) {
 					void* w;
-					SYZ_TRY(ws_get(ctx, 15, (npairs + 4 * gcnt) * 8 + 64, &w));
+					SYZ_TRY(ws_get(ctx, kWsPairs, (npairs + 4 * gcnt) * 8 + 64, &w));
 					if (npairs)
 						SYZ_HIP(hipMemcpyAsync(w, pr, npairs * 8, hipMemcpyDeviceToDevice, s));
 					pr = w;
 				}
 			} else {
-				SYZ_TRY(ws_grow_keep(ctx, 15, (npairs + 4 * gcnt) * 8 + 64, npairs * 8, &pr));
+				SYZ_TRY(ws_grow_keep(ctx, kWsPairs, (npairs + 4 * gcnt) * 8 + 64, npairs * 8, &pr));
 			}
 			*pairs_out = (uint64_t*)pr;
-			SYZ_TRY(counters_reset(ctx));
-			memcpy(ctx->h_pin + kPinPairs, &npairs, 8);
-			SYZ_HIP(hipMemcpyAsync(&ctx->d_cnt[kCntAux2], ctx->h_pin + kPinPairs, 8, hipMemcpyHostToDevice, s));
+			SYZ_TRY(seed_pair_counter(ctx, npairs));
 			k_agg_finalize<<<(uint32_t)rc.size(), kFinThreads, 0, s>>>(
 			    (const uint32_t*)de2, (const uint4*)df2, (const uint32_t*)dc2, (uint32_t)rc.size(), lm, c0, ms->slots,
 			    ms->nbuckets - 1, nsp->slots, nsp->nbuckets - 1, b->call_new, (uint64_t*)pr, &ctx->d_cnt[kCntAux2],
@@ -2962,11 +3000,10 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 		}
 		st->overflow_parts += novf;
 	}
-	if (fresh_ns && changed == 0) {
-		syzsig_set_free(nsp);
-		*ns = nullptr;
+	if (changed)
+		fresh.keep();
+	else if (fresh.drop())
 		nsp = nullptr;
-	}
 	ms->len += inserted;
 	if (nsp)
 		nsp->len += ns_ins;
@@ -2984,27 +3021,39 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 	return SYZSIG_OK;
 }
 
+// The one-sync run where capped cells are in use, attempted once more when the
+// first attempt asks for more partitions.  *done = false with agg_counted_once
+// set after a spilled cell: the run is redone with counted cells, not capped
+// ones again.
+static int agg_triage_one_sync(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsig_batch* b, uint64_t c0,
+                               uint64_t c1, const LevelMap& lm, uint64_t run_recs, syzsig_batch_stats* st,
+                               uint64_t** pairs, uint64_t* npairs, bool fast, bool* done)
+{
+	*done = false;
+	if (ctx->cap_sd <= 0 || ctx->agg_counted_once ||
+	    (ctx->agg_dbg & (SYZSIG_DEBUG_EXACT_CELLS | SYZSIG_DEBUG_CAP_SPILL | kDebugAtomicFinalize)))
+		return SYZSIG_OK;
+	bool bad = false, regeom = false;
+	uint64_t retries0 = st->retries;
+	SYZ_TRY(agg_triage_fused(ctx, ms, ns, b, c0, c1, lm, run_recs, st, pairs, npairs, done, fast, &bad, &regeom));
+	if (regeom) {  // once more with partitions for what the first attempt counted
+		retries0 = st->retries;
+		SYZ_TRY(agg_triage_fused(ctx, ms, ns, b, c0, c1, lm, run_recs, st, pairs, npairs, done, fast, &bad, &regeom));
+	}
+	ctx->agg_counted_once = !*done && st->retries != retries0;
+	return SYZSIG_OK;
+}
+
 // One run of calls [c0, c1) with level map lm.  Pairs are appended at
 // pairs[*npairs_io ...] (internal buffer, grown as needed).
 int agg_triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsig_batch* b, uint64_t c0, uint64_t c1,
                    const LevelMap& lm, uint64_t run_recs, syzsig_batch_stats* st, uint64_t** pairs_out,
                    uint64_t* npairs_io)
 {
-	if (ctx->cap_sd > 0 && !(ctx->agg_dbg & (SYZSIG_DEBUG_EXACT_CELLS | SYZSIG_DEBUG_CAP_SPILL | 16)) &&
-	    !ctx->agg_counted_once) {
-		bool done = false, regeom = false;
-		uint64_t retries0 = st->retries;
-		SYZ_TRY(agg_triage_fused(ctx, ms, ns, b, c0, c1, lm, run_recs, st, pairs_out, npairs_io, &done, false,
-		                         nullptr, &regeom));
-		if (regeom) {  // once more with partitions for what the first attempt counted
-			retries0 = st->retries;
-			SYZ_TRY(agg_triage_fused(ctx, ms, ns, b, c0, c1, lm, run_recs, st, pairs_out, npairs_io, &done));
-		}
-		if (done)
-			return SYZSIG_OK;
-		// a spilled cell: this run is redone with counted cells, not capped ones again
-		ctx->agg_counted_once = st->retries != retries0;
-	}
+	bool done = false;
+	SYZ_TRY(agg_triage_one_sync(ctx, ms, ns, b, c0, c1, lm, run_recs, st, pairs_out, npairs_io, false, &done));
+	if (done)
+		return SYZSIG_OK;
 	AggOut a;
 	SYZ_TRY(agg_aggregate(ctx, b, c0, c1, lm, run_recs, st, &a));
 	const uint64_t D = a.D;
@@ -3012,10 +3061,8 @@ int agg_triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsi
 	void* pr;
 	// capacity for every possible change, then finalize (never retried)
 	SYZ_TRY(set_reserve(ms, D));
-	// newSignal.Merge allocates a nil receiver (signal.go:121-125) -- but only
-	// when some DiffRaw is non-empty: a fresh set is dropped again if nothing changed
-	const bool fresh_ns = D && !*ns;
-	if (fresh_ns)
+	FreshNs fresh(ns, D && !*ns);
+	if (fresh.armed)
 		SYZ_TRY(syzsig_set_make(ctx, D, ns));
 	// newSignal takes up to D changes per batch: kept at most half full, so its
 	// probe chains stay short in the finalize (0.34 -> 0.28 ms at C2)
@@ -3027,35 +3074,20 @@ int agg_triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsi
 		SYZ_TRY(reserve_slices(ctx, *ns, a.dist_e, a.cnt, a.parts, a.nregions, pb));
 	}
 	const uint64_t need_pairs = *npairs_io + 4 * D;
-	SYZ_TRY(ws_grow_keep(ctx, 15, need_pairs * 8 + 64, *npairs_io * 8, &pr));
+	SYZ_TRY(ws_grow_keep(ctx, kWsPairs, need_pairs * 8 + 64, *npairs_io * 8, &pr));
 	*pairs_out = (uint64_t*)pr;
-	SYZ_TRY(counters_reset(ctx));
-	memcpy(ctx->h_pin + kPinPairs, npairs_io, 8);  // consumed before the counters_fetch below
-	SYZ_HIP(hipMemcpyAsync(&ctx->d_cnt[kCntAux2], ctx->h_pin + kPinPairs, 8, hipMemcpyHostToDevice, s));
+	SYZ_TRY(seed_pair_counter(ctx, *npairs_io));
 	syzsig_set* nsp = *ns;
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[2], s));
 	// the slice-exclusive finalize when every region is a partition and both
 	// tables have at least one bucket per partition; else the atomic one
 	const bool fx = D && nsp && a.nregions == a.parts && ms->nbuckets >= a.parts && nsp->nbuckets >= a.parts &&
-	                !(ctx->agg_dbg & 16);
+	                !(ctx->agg_dbg & kDebugAtomicFinalize);
 	if (fx) {
-		const uint32_t pb = 31 - __builtin_clz(a.parts);
-		const uint32_t ms_shift = (63 - __builtin_clzll(ms->nbuckets)) - pb;
-		const uint32_t ns_shift = (63 - __builtin_clzll(nsp->nbuckets)) - pb;
-		void *dd, *dn;
-		SYZ_TRY(ws_get(ctx, 32, D * 20 + 64, &dd));
-		SYZ_TRY(ws_get(ctx, 33, D * 8 + 64, &dn));
-		uint32_t* def_e = (uint32_t*)dd;
-		uint4* def_f = (uint4*)((char*)dd + ((D * 4 + 15) & ~15ull));
-		k_agg_finalize_x<2><<<a.nregions, kFxThreads, 0, s>>>(
-		    a.dist_e, a.dist_f, a.cnt, a.nregions, lm, c0, ms->slots, ms->nbuckets - 1, ms_shift, nsp->slots,
-		    nsp->nbuckets - 1, ns_shift, b->call_new, (uint64_t*)pr, &ctx->d_cnt[kCntAux2], ctx->d_cnt, def_e, def_f,
-		    &ctx->d_cnt[kCntDefer], (uint64_t*)dn, &ctx->d_cnt[kCntDeferNs], ctx->agg_dbg, nullptr, nullptr, 0);
-		k_fin_deferred<<<2 * kDeferBlocks, 256, 0, s>>>(def_e, def_f, &ctx->d_cnt[kCntDefer], lm, c0, ms->slots,
-		                                                ms->nbuckets - 1, nsp->slots, nsp->nbuckets - 1, b->call_new,
-		                                                (uint64_t*)pr, &ctx->d_cnt[kCntAux2], ctx->d_cnt,
-		                                                (const uint64_t*)dn, &ctx->d_cnt[kCntDeferNs]);
+		FinArgs fa;
+		SYZ_TRY(fin_args(ctx, ms, nsp, 31 - __builtin_clz(a.parts), lm, c0, b, (uint64_t*)pr, D, &fa));
+		SYZ_TRY(fin_launch(ctx, fa, a.dist_e, a.dist_f, a.cnt, a.nregions));
 	} else if (D) {
 		k_agg_finalize<<<a.nregions, kFinThreads, 0, s>>>(
 		    a.dist_e, a.dist_f, a.cnt, a.nregions, lm, c0, ms->slots,
@@ -3073,11 +3105,10 @@ int agg_triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsi
 	}
 	if (ctx->h_cnt[kCntOverflow])
 		return fail(SYZSIG_EIO, "triage: table overflow after reserve (internal error; planned run)");
-	if (fresh_ns && ctx->h_cnt[kCntChanged] == 0) {
-		syzsig_set_free(*ns);
-		*ns = nullptr;
+	if (ctx->h_cnt[kCntChanged])
+		fresh.keep();
+	else if (fresh.drop())
 		nsp = nullptr;
-	}
 	ms->len += ctx->h_cnt[kCntInserted];
 	st->inserted += ctx->h_cnt[kCntInserted];
 	st->changed += ctx->h_cnt[kCntChanged];
@@ -3092,24 +3123,10 @@ int agg_triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsi
 int agg_triage_optimistic(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsig_batch* b,
                           syzsig_batch_stats* st, uint64_t** pairs, uint64_t* npairs, bool* done)
 {
-	*done = false;
-	if (ctx->cap_sd <= 0 || ctx->agg_counted_once ||
-	    (ctx->agg_dbg & (SYZSIG_DEBUG_EXACT_CELLS | SYZSIG_DEBUG_CAP_SPILL | 16)))
-		return SYZSIG_OK;
 	LevelMap lm;
 	const int8_t lv[4] = {0, 1, 2, 3};
 	SYZ_TRY(level_map_from_levels(lv, 4, &lm));
-	bool bad = false, regeom = false;
-	uint64_t retries0 = st->retries;
-	SYZ_TRY(agg_triage_fused(ctx, ms, ns, b, 0, b->ncalls, lm, b->nrec, st, pairs, npairs, done, true, &bad,
-	                         &regeom));
-	if (regeom) {  // once more with partitions for what the first attempt counted
-		retries0 = st->retries;
-		SYZ_TRY(agg_triage_fused(ctx, ms, ns, b, 0, b->ncalls, lm, b->nrec, st, pairs, npairs, done, true, &bad));
-	}
-	// a spilled cell: the planned path redoes the batch with counted cells
-	ctx->agg_counted_once = !*done && st->retries != retries0;
-	return SYZSIG_OK;
+	return agg_triage_one_sync(ctx, ms, ns, b, 0, b->ncalls, lm, b->nrec, st, pairs, npairs, true, done);
 }
 
 // Per-record bits of calls [c0, c1) from the run's pairs [p0, p1).
@@ -3120,7 +3137,7 @@ int agg_mark_bits(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t 
 		return SYZSIG_OK;
 	const uint64_t n = p1 - p0, C = pow2_at_least(2 * n + 16);
 	void* set;
-	SYZ_TRY(ws_get(ctx, 14, C * 8, &set));
+	SYZ_TRY(ws_get(ctx, kWsPairSet, C * 8, &set));
 	const hipStream_t s = ctx->stream;
 	SYZ_HIP(hipMemsetAsync(set, 0xff, C * 8, s));
 	SYZ_TRY(counters_reset(ctx));
@@ -3137,7 +3154,7 @@ int pairs_from_bits(syzsig_ctx* ctx, const syzsig_batch* b, const uint32_t* bits
 {
 	const hipStream_t s = ctx->stream;
 	void *raw, *set, *out;
-	SYZ_TRY(ws_get(ctx, 13, bound * 8 + 64, &raw));
+	SYZ_TRY(ws_get(ctx, kWsPairsRaw, bound * 8 + 64, &raw));
 	SYZ_TRY(counters_reset(ctx));
 	k_bits_to_pairs<<<grid_for((c1 - c0) * 64, 256, 8192), 256, 0, s>>>(b->sigs, b->call_start, b->call_len, c0, c1,
 	                                                                     b->call_new, bits, (uint64_t*)raw,
@@ -3148,13 +3165,11 @@ int pairs_from_bits(syzsig_ctx* ctx, const syzsig_batch* b, const uint32_t* bits
 	if (n == 0)
 		return SYZSIG_OK;
 	const uint64_t C = pow2_at_least(2 * n + 16);
-	SYZ_TRY(ws_get(ctx, 14, C * 8, &set));
+	SYZ_TRY(ws_get(ctx, kWsPairSet, C * 8, &set));
 	SYZ_HIP(hipMemsetAsync(set, 0xff, C * 8, s));
-	SYZ_TRY(ws_grow_keep(ctx, 15, (*npairs_io + n) * 8 + 64, *npairs_io * 8, &out));
+	SYZ_TRY(ws_grow_keep(ctx, kWsPairs, (*npairs_io + n) * 8 + 64, *npairs_io * 8, &out));
 	*pairs_io = (uint64_t*)out;
-	SYZ_TRY(counters_reset(ctx));
-	memcpy(ctx->h_pin + kPinPairs, npairs_io, 8);  // consumed before the counters_fetch below
-	SYZ_HIP(hipMemcpyAsync(&ctx->d_cnt[kCntAux2], ctx->h_pin + kPinPairs, 8, hipMemcpyHostToDevice, s));
+	SYZ_TRY(seed_pair_counter(ctx, *npairs_io));
 	k_pairs_set<<<grid_for(n, 256, 8192), 256, 0, s>>>((const uint64_t*)raw, n, (uint64_t*)set, C,
 	                                                   &ctx->d_cnt[kCntAux]);
 	k_pairs_compact<<<grid_for(C, 256, 8192), 256, 0, s>>>((const uint64_t*)set, C, (uint64_t*)out,
@@ -3350,7 +3365,7 @@ int syzsig_step_send_dev(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t serial
 	const hipStream_t s = ctx->stream;
 	unsigned long long* sc = ctx->d_step + kStepSrc;
 	void* wcur;
-	SYZ_TRY(ws_get(ctx, 63, kMaxShardsAgg * 8 + 64, &wcur));
+	SYZ_TRY(ws_get(ctx, kWsStepCursor, kMaxShardsAgg * 8 + 64, &wcur));
 	unsigned long long* cursor = (unsigned long long*)wcur;
 	ctx->step_src_timed = ctx->timing;
 	if (ctx->timing)
@@ -3368,35 +3383,14 @@ int syzsig_step_send_dev(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t serial
 		// one-sync triage run): prios among `levels`, valid ranges, <= nrec records
 		AggGeom g = agg_geom_for(ctx, b->nrec, 0);
 		g.ibits = g.cbits();
-		const uint32_t S = 1u << g.pbits, P = S;
-		const uint64_t nchunks = (b->ncalls + (1ull << g.ibits) - 1) >> g.ibits;
-		const float sd = ctx->cap_sd;
+		const uint32_t P = 1u << g.pbits;
 		ctx->step_src_parts = P;
-		const uint64_t bound = b->nrec + b->nrec / 4 + nchunks * S * (uint64_t)(sd * sd + 128.0f) + 64;
-		void *recs, *cm, *dc, *de, *df, *dpart;
-		SYZ_TRY(ws_get(ctx, 16, (bound + kDummyLines * kBlk) * 4, &recs));
-		SYZ_TRY(ws_get(ctx, 17, nchunks * 24 + (uint64_t)S * nchunks * 4 + 256, &cm));
-		SYZ_TRY(ws_get(ctx, 21, (uint64_t)(P + 1) * 4 + 64, &dc));
-		SYZ_TRY(ws_get(ctx, 19, (uint64_t)P * kAggRegion * 4 + 64, &de));
-		SYZ_TRY(ws_get(ctx, 20, (uint64_t)P * kAggRegion * 16 + 64, &df));
-		SYZ_TRY(ws_get(ctx, 54, nchunks * 16 + 64, &dpart));
-		uint64_t* sizes = (uint64_t*)cm;
-		uint64_t* cbase = sizes + nchunks;
-		uint32_t* ccap = (uint32_t*)(cbase + nchunks);
-		uint32_t* ccnt = ccap + nchunks;
-		uint32_t* tiles = ccnt + (uint64_t)S * nchunks;
-		uint32_t* ovf = (uint32_t*)&sc[kCntSpill];
-		k_fast_prep<<<(uint32_t)nchunks, 256, 0, s>>>(b->call_start, b->call_len, b->call_prio, 0, b->ncalls, g.ibits,
-		                                              b->nrec, sizes, (uint64_t*)dpart, b->call_new, lm, tiles);
-		k_cell_plan_fast<<<1, 1024, 0, s>>>(sizes, nchunks, S, sd, cbase, ccap, (const uint64_t*)dpart, b->nrec, 0, sc);
-		const CapCells cc{cbase, ccap, ccnt, ovf, nchunks, (uint32_t*)recs + bound, sizes, tiles, false, kScat3Tile};
-		scatter_triage(nchunks, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, 0, b->ncalls, g,
-		               AggSrc{nullptr, 1, 0, 0}, cc, (uint32_t*)recs, ctx->agg_dbg >> 10);
-		const AggCells xc{(const uint32_t*)recs, nullptr, nullptr, cbase, ccap, ccnt, nchunks, 0, agg_group_size(nchunks),
-		                  ovf, sc};
-		launch_agg<true>(ctx, bound, P, s, xc, g, de, df, dc);
+		CapRun r;
+		SYZ_TRY(cap_layout(ctx, b->nrec, nchunks_of(b->ncalls, g.ibits), P, ctx->cap_sd, &r));
+		SYZ_TRY(cap_plan(ctx, b, 0, b->ncalls, lm, g, b->nrec, &r, kScat3Tile, sc));
+		SYZ_TRY(cap_scatter_agg(ctx, b, 0, b->ncalls, lm, g, r, kScat3Tile, nullptr, sc, nullptr));
 		k_stair_bucket<<<(int)std::min<uint32_t>(P, 2048), 256, 0, s>>>(
-		    (const uint32_t*)de, (const uint4*)df, (const uint32_t*)dc, P, lm.n, nshards, serial_base, cap, cursor,
+		    (const uint32_t*)r.de, (const uint4*)r.df, (const uint32_t*)r.dc, P, lm.n, nshards, serial_base, cap, cursor,
 		    d_send, sc);
 		SYZ_HIP(hipGetLastError());
 	} else {
@@ -3460,7 +3454,7 @@ int syzsig_step_back_dev(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t serial
 		SYZ_HIP(hipStreamSynchronize(s));
 		const uint64_t np0 = hb[kCntAux2], bound = np0 + (uint64_t)nshards * cap;
 		void* wp;
-		SYZ_TRY(ws_grow_keep(ctx, 55, bound * 8 + 64, np0 * 8, &wp));
+		SYZ_TRY(ws_grow_keep(ctx, kWsStepPairs, bound * 8 + 64, np0 * 8, &wp));
 		k_step_back<<<grid, 256, 0, s>>>(d_send, d_back, cap, serial_base, b->call_new, (uint64_t*)wp, bound, bc);
 		SYZ_HIP(hipGetLastError());
 		SYZ_HIP(hipMemcpyAsync(hb, bc, kNumCounters * 8, hipMemcpyDeviceToHost, s));

@@ -817,9 +817,6 @@ static size_t cm_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static int cm_grid(uint64_t n) { return (int)std::min<uint64_t>(std::max<uint64_t>(n, 1), 1u << 20); }
 
-// workspace slots (shared with cover.hip, whose calls never overlap these)
-constexpr int kWsMeta = 48, kWsTab = 49, kWsBufA = 50, kWsBufB = 51, kWsStage = 52, kWsStage2 = 37;
-
 // The sort-unique of every segment of S (lengths and counts as the prep
 // kernel left them in ctx->h_cnt).  Enqueues only.
 template <int W, typename Pol>
@@ -834,9 +831,9 @@ static int cm_sort_unique(syzsig_ctx* ctx, const CmSegs& S, const Pol& pol)
 		void *ba, *bb;
 		const size_t o_base = cm_align(nlarge * 8), o_tlg = o_base + cm_align(nlarge * 8),
 		             o_tix = o_tlg + cm_align(ntiles * 4);
-		SYZ_TRY(ws_get(ctx, kWsTab, o_tix + cm_align(ntiles * 4), (void**)&tab));
-		SYZ_TRY(ws_get(ctx, kWsBufA, nkeys * 8 * W + 256, &ba));
-		SYZ_TRY(ws_get(ctx, kWsBufB, nkeys * 8 * W + 256, &bb));
+		SYZ_TRY(ws_get(ctx, kWsSuTab, o_tix + cm_align(ntiles * 4), (void**)&tab));
+		SYZ_TRY(ws_get(ctx, kWsSuBufA, nkeys * 8 * W + 256, &ba));
+		SYZ_TRY(ws_get(ctx, kWsSuBufB, nkeys * 8 * W + 256, &bb));
 		uint64_t* lg_seg = (uint64_t*)tab;
 		uint64_t* lg_base = (uint64_t*)(tab + o_base);
 		uint32_t* tile_lg = (uint32_t*)(tab + o_tlg);
@@ -915,7 +912,7 @@ extern "C" int syzsig_exec_comps_dev(syzsig_ctx* ctx, const uint64_t* d_comps, u
 		return SYZSIG_OK;
 	const hipStream_t s = ctx->stream;
 	void* seg_len;
-	SYZ_TRY(ws_get(ctx, kWsMeta, ncalls * 4 + 256, &seg_len));
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, ncalls * 4 + 256, &seg_len));
 	SYZ_TRY(counters_reset(ctx));
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
@@ -960,7 +957,7 @@ extern "C" int syzsig_comp_map_dev(syzsig_ctx* ctx, const uint32_t* d_words, uin
 	char* d;
 	const size_t o_ps = cm_align((ncalls + 1) * 8), o_pl = o_ps + cm_align(ncalls * 8), o_sl = o_pl + cm_align(ncalls * 4),
 	             o_cnt = o_sl + cm_align(ncalls * 4), o_off = o_cnt + cm_align(ncalls * 4), o_st = o_off + cm_align((ncalls + 1) * 8);
-	SYZ_TRY(ws_get(ctx, kWsMeta, o_st + cm_align(ncalls * 4), (void**)&d));
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_st + cm_align(ncalls * 4), (void**)&d));
 	uint64_t *rec_base = (uint64_t*)d, *pair_start = (uint64_t*)(d + o_ps), *off = (uint64_t*)(d + o_off);
 	uint32_t *pair_len = (uint32_t*)(d + o_pl), *seg_len = (uint32_t*)(d + o_sl), *cnt = (uint32_t*)(d + o_cnt);
 	int32_t* status = (int32_t*)(d + o_st);
@@ -980,8 +977,8 @@ extern "C" int syzsig_comp_map_dev(syzsig_ctx* ctx, const uint32_t* d_words, uin
 	SYZ_HIP(hipMemcpyAsync(&nrec, rec_base + ncalls, 8, hipMemcpyDeviceToHost, s));
 	SYZ_HIP(hipStreamSynchronize(s));
 	void *stage, *stage2;  // two pairs of two words per record
-	SYZ_TRY(ws_get(ctx, kWsStage, nrec * 32 + 256, &stage));
-	SYZ_TRY(ws_get(ctx, kWsStage2, nrec * 32 + 256, &stage2));
+	SYZ_TRY(ws_get(ctx, kWsSuStage, nrec * 32 + 256, &stage));
+	SYZ_TRY(ws_get(ctx, kWsSuStage2, nrec * 32 + 256, &stage2));
 	k_cm_walk<<<(int)((ncalls + 63) / 64), 64, 0, s>>>(d_words, d_comps_start, d_comps_cnt, d_comps_end, ncalls,
 	                                                   nwords, rec_base, (uint64_t*)stage, pair_start, pair_len,
 	                                                   status);
@@ -1023,7 +1020,7 @@ extern "C" int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_o
 	const size_t o_voff = cm_align(nv * 8), o_vcnt = o_voff + cm_align((nv + 1) * 8), o_sl = o_vcnt + cm_align(nv * 4),
 	             o_seg = o_sl + cm_align(nv * 4), o_cnt = o_seg + cm_align(nq * 4), o_off = o_cnt + cm_align(nq * 4),
 	             o_sp = o_off + cm_align((nq + 1) * 8);
-	SYZ_TRY(ws_get(ctx, kWsMeta, o_sp + cm_align((size_t)nspecial * 8 + 8), (void**)&d));
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_sp + cm_align((size_t)nspecial * 8 + 8), (void**)&d));
 	uint64_t *vlo = (uint64_t*)d, *voff = (uint64_t*)(d + o_voff), *off = (uint64_t*)(d + o_off),
 	         *special = (uint64_t*)(d + o_sp);
 	uint32_t *vcnt = (uint32_t*)(d + o_vcnt), *src_len = (uint32_t*)(d + o_sl), *seg_len = (uint32_t*)(d + o_seg),
@@ -1048,8 +1045,8 @@ extern "C" int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_o
 		return fail(SYZSIG_EINVAL, "shrink_expand: a query's call is outside the map, or the map's offsets are not "
 		                           "ascending inside its pairs");
 	void *cand, *stage2;
-	SYZ_TRY(ws_get(ctx, kWsStage, ncand * 8 + 256, &cand));
-	SYZ_TRY(ws_get(ctx, kWsStage2, ncand * 8 + 256, &stage2));
+	SYZ_TRY(ws_get(ctx, kWsSuStage, ncand * 8 + 256, &cand));
+	SYZ_TRY(ws_get(ctx, kWsSuStage2, ncand * 8 + 256, &stage2));
 	k_se_write<<<(int)((nq + 3) / 4), 256, 0, s>>>(d_pairs, d_q_val, nq, vlo, vcnt, voff, special, nspecial,
 	                                               (uint64_t*)cand, src_len);
 	k_cm_prep_sources<<<(int)((nq + 255) / 256), 256, 0, s>>>(src_len, kCmVariants, nq, seg_len, ctx->d_cnt);

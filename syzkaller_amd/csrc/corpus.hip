@@ -524,11 +524,11 @@ static int ni_accept_batched(syzsig_ctx* ctx, const NiBatch& B, const syzsig_set
 		d += B.sig_len(i);
 	}
 	void *dtab, *dx, *drec, *dev, *dacc;
-	SYZ_TRY(ni_upload(ctx, 43, tab.data(), (size_t)R * 24, &dtab));
-	SYZ_TRY(ws_get(ctx, 44, nA * 8 + 64, &dx));
-	SYZ_TRY(ws_get(ctx, 45, ni_align(nA * 4) + nA + 64, &drec));
-	SYZ_TRY(ws_get(ctx, 46, nA * 8 + 64, &dev));
-	SYZ_TRY(ws_get(ctx, 47, (size_t)K + 64, &dacc));
+	SYZ_TRY(ni_upload(ctx, kWsNiStageA, tab.data(), (size_t)R * 24, &dtab));
+	SYZ_TRY(ws_get(ctx, kWsNiStageB, nA * 8 + 64, &dx));
+	SYZ_TRY(ws_get(ctx, kWsNiRecs, ni_align(nA * 4) + nA + 64, &drec));
+	SYZ_TRY(ws_get(ctx, kWsNiEvents, nA * 8 + 64, &dev));
+	SYZ_TRY(ws_get(ctx, kWsNiAccepted, (size_t)K + 64, &dacc));
 	uint32_t* rec_row = (uint32_t*)drec;
 	int8_t* rec_prio = (int8_t*)((char*)drec + ni_align(nA * 4));
 	SYZ_HIP(hipMemsetAsync(dacc, 0, K, s));
@@ -640,16 +640,16 @@ static int ni_merge_keys(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, 
 			t_idx[b++] = t;
 		}
 	void *drt, *dgt, *dtt, *dkeys, *dba, *dbb = nullptr, *dent, *dst_, *dgcov;
-	SYZ_TRY(ni_upload(ctx, 24, rt.data(), (size_t)M * 44, &drt));
-	SYZ_TRY(ni_upload(ctx, 29, gt.data(), (size_t)G * 12, &dgt));
-	SYZ_TRY(ni_upload(ctx, 53, tt.data(), (size_t)ntiles * 8, &dtt));
-	SYZ_TRY(ws_get(ctx, 25, nM * 8 + 64, &dkeys));
-	SYZ_TRY(ws_get(ctx, 26, nM * 8 + 64, &dba));
+	SYZ_TRY(ni_upload(ctx, kWsNiRecTab, rt.data(), (size_t)M * 44, &drt));
+	SYZ_TRY(ni_upload(ctx, kWsNiGroupTab, gt.data(), (size_t)G * 12, &dgt));
+	SYZ_TRY(ni_upload(ctx, kWsNiTiles, tt.data(), (size_t)ntiles * 8, &dtt));
+	SYZ_TRY(ws_get(ctx, kWsNiKeys, nM * 8 + 64, &dkeys));
+	SYZ_TRY(ws_get(ctx, kWsNiBufA, nM * 8 + 64, &dba));
 	if (maxlen > kNiTile)
-		SYZ_TRY(ws_get(ctx, 27, nM * 8 + 64, &dbb));
-	SYZ_TRY(ws_get(ctx, 28, ni_align(nM * 4) + nM + 64, &dent));
-	SYZ_TRY(ws_get(ctx, 34, ni_align(nM * 4) + ni_align(nM) + ni_align((size_t)G * 4) + ((size_t)G + 1) * 8 + 64, &dst_));
-	SYZ_TRY(ws_get(ctx, 38, cM * 4 + 64, &dgcov));
+		SYZ_TRY(ws_get(ctx, kWsNiBufB, nM * 8 + 64, &dbb));
+	SYZ_TRY(ws_get(ctx, kWsNiEntries, ni_align(nM * 4) + nM + 64, &dent));
+	SYZ_TRY(ws_get(ctx, kWsNiState, ni_align(nM * 4) + ni_align(nM) + ni_align((size_t)G * 4) + ((size_t)G + 1) * 8 + 64, &dst_));
+	SYZ_TRY(ws_get(ctx, kWsNiGroupCover, cM * 4 + 64, &dgcov));
 	const uint64_t* drt64 = (const uint64_t*)drt;
 	const uint32_t* drt32 = (const uint32_t*)(drt64 + 4 * (size_t)M);
 	const NiRows R{drt64, drt64 + M, drt64 + 2 * (size_t)M, drt64 + 3 * (size_t)M, drt32, drt32 + M, drt32 + 2 * (size_t)M, M};
@@ -680,7 +680,7 @@ static int ni_merge_keys(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, 
 		off[g + 1] = off[g] + std::min<uint32_t>(cnt[g], g_len[g]);
 	const uint64_t total = off[G];
 	void* dout;
-	SYZ_TRY(ws_get(ctx, 36, ni_align(total * 4) + total + 64, &dout));
+	SYZ_TRY(ws_get(ctx, kWsNiOut, ni_align(total * 4) + total + 64, &dout));
 	int8_t* out_p = (int8_t*)((char*)dout + ni_align(total * 4));
 	SYZ_HIP(hipMemcpyAsync(d_off, off.data(), ((size_t)G + 1) * 8, hipMemcpyHostToDevice, s));
 	k_ni_csr<<<ni_grid(G), kNiThreads, 0, s>>>(st_e, st_p, dg_base, d_off, G, (uint32_t*)dout, out_p);
@@ -714,8 +714,8 @@ static int ni_merge_keys(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, 
 		std::copy(gc_len.begin(), gc_len.end(), (uint32_t*)(it.data() + o_cl));
 		char* dit;
 		void* dcout;
-		SYZ_TRY(ni_upload(ctx, 54, it.data(), o_end, (void**)&dit));
-		SYZ_TRY(ws_get(ctx, 35, cM * 4 + 64, &dcout));
+		SYZ_TRY(ni_upload(ctx, kWsNiItems, it.data(), o_end, (void**)&dit));
+		SYZ_TRY(ws_get(ctx, kWsNiCoverOut, cM * 4 + 64, &dcout));
 		uint64_t ctot = 0;
 		SYZ_TRY(syzsig_triage_cover_dev(ctx, G, 1, (const uint8_t*)dit, (const uint8_t*)(dit + o_keep),
 		                                (const uint64_t*)(dit + o_roff), (const int32_t*)(dit + o_errno),
@@ -781,11 +781,11 @@ static int ni_commit(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, NiAc
 	}
 	SYZ_TRY(set_reserve(cv, cacc));
 	void *dfl, *dco;
-	SYZ_TRY(ni_upload(ctx, 43, B.flags, B.K, &dfl));
+	SYZ_TRY(ni_upload(ctx, kWsNiStageA, B.flags, B.K, &dfl));
 	std::vector<uint64_t> co((size_t)B.K + 1);
 	for (uint32_t i = 0; i <= B.K; i++)
 		co[i] = B.cover_off[i] - B.cover_off[0];
-	SYZ_TRY(ni_upload(ctx, 44, co.data(), ((size_t)B.K + 1) * 8, &dco));
+	SYZ_TRY(ni_upload(ctx, kWsNiStageB, co.data(), ((size_t)B.K + 1) * 8, &dco));
 	SYZ_TRY(counters_reset(ctx));
 	const uint32_t eb = (uint32_t)grid_for(A->E, kNiThreads, 8192), rb = cacc ? (uint32_t)ni_grid(B.K) : 0;
 	k_ni_commit<<<eb + rb, kNiThreads, 0, s>>>(A->d_ev, A->E, eb, cs->slots, cs->nbuckets - 1, A->d_acc,
@@ -853,9 +853,9 @@ extern "C" int syzsig_manager_new_input_batch(syzsig_ctx* ctx, syzsig_set** corp
 	std::fill(ctx->ni_stats, ctx->ni_stats + 4, 0);
 	NiBatch B{K, nkeys, input_key, input_flags, sig_off, cover_off, elems, prios, cover, n_all, c_all, nullptr, nullptr, nullptr};
 	void *de, *dp, *dc;
-	SYZ_TRY(ni_upload(ctx, 40, n_all ? elems + sig_off[0] : nullptr, n_all * 4, &de));
-	SYZ_TRY(ni_upload(ctx, 41, n_all ? prios + sig_off[0] : nullptr, n_all, &dp));
-	SYZ_TRY(ni_upload(ctx, 42, c_all ? cover + cover_off[0] : nullptr, c_all * 4, &dc));
+	SYZ_TRY(ni_upload(ctx, kWsNiElems, n_all ? elems + sig_off[0] : nullptr, n_all * 4, &de));
+	SYZ_TRY(ni_upload(ctx, kWsNiPrios, n_all ? prios + sig_off[0] : nullptr, n_all, &dp));
+	SYZ_TRY(ni_upload(ctx, kWsNiCover, c_all ? cover + cover_off[0] : nullptr, c_all * 4, &dc));
 	B.d_elems = (const uint32_t*)de;
 	B.d_prios = (const int8_t*)dp;
 	B.d_cover = (const uint32_t*)dc;

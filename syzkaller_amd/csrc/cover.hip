@@ -587,9 +587,9 @@ static int cv_sort_unique(syzsig_ctx* ctx, const CvSegs& S)
 		void *ba, *bb;
 		const size_t o_base = cv_align(nlarge * 8), o_tlg = o_base + cv_align(nlarge * 8),
 		             o_tix = o_tlg + cv_align(ntiles * 4);
-		SYZ_TRY(ws_get(ctx, 49, o_tix + cv_align(ntiles * 4), (void**)&tab));
-		SYZ_TRY(ws_get(ctx, 50, nkeys * 4 + 256, &ba));
-		SYZ_TRY(ws_get(ctx, 51, nkeys * 4 + 256, &bb));
+		SYZ_TRY(ws_get(ctx, kWsSuTab, o_tix + cv_align(ntiles * 4), (void**)&tab));
+		SYZ_TRY(ws_get(ctx, kWsSuBufA, nkeys * 4 + 256, &ba));
+		SYZ_TRY(ws_get(ctx, kWsSuBufB, nkeys * 4 + 256, &bb));
 		uint64_t* lg_seg = (uint64_t*)tab;
 		uint64_t* lg_base = (uint64_t*)(tab + o_base);
 		uint32_t* tile_lg = (uint32_t*)(tab + o_tlg);
@@ -628,7 +628,7 @@ extern "C" int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uin
 		return SYZSIG_OK;
 	const hipStream_t s = ctx->stream;
 	void* seg_len;
-	SYZ_TRY(ws_get(ctx, 48, ncalls * 4 + 256, &seg_len));
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, ncalls * 4 + 256, &seg_len));
 	SYZ_TRY(counters_reset(ctx));
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
@@ -690,7 +690,7 @@ extern "C" int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_
 	char* d;
 	const size_t o_seg = cv_align(nruns * 4), o_cnt = o_seg + cv_align(nitems * 4), o_soff = o_cnt + cv_align(nitems * 4),
 	             o_off = o_soff + cv_align((nitems + 1) * 8);
-	SYZ_TRY(ws_get(ctx, 48, o_off + cv_align((nitems + 1) * 8), (void**)&d));
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_off + cv_align((nitems + 1) * 8), (void**)&d));
 	uint32_t *src_len = (uint32_t*)d, *seg_len = (uint32_t*)(d + o_seg), *cnt = (uint32_t*)(d + o_cnt);
 	uint64_t *stage_off = (uint64_t*)(d + o_soff), *off = (uint64_t*)(d + o_off);
 	SYZ_TRY(counters_reset(ctx));
@@ -707,7 +707,7 @@ extern "C" int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_
 	if (ctx->h_cnt[kCntOverflow])
 		return fail(SYZSIG_ERANGE, "triage_cover: an item's runs hold 2^31 or more PCs");
 	void* stage;
-	SYZ_TRY(ws_get(ctx, 52, ctx->h_cnt[kCvTotal] * 4 + 256, &stage));
+	SYZ_TRY(ws_get(ctx, kWsSuStage, ctx->h_cnt[kCvTotal] * 4 + 256, &stage));
 	const CvSegs S{d_cover, d_run_cover_start, src_len, runs, seg_len, nitems, (uint32_t*)stage, stage_off, cnt};
 	SYZ_TRY(cv_sort_unique<false>(ctx, S));
 	k_cover_scan<<<1, kCvThreads, 0, s>>>(cnt, nitems, off);

@@ -69,12 +69,130 @@ struct Workspace {
 	size_t size = 0;
 };
 
+// The context's grow-only scratch buffers (syzsig_ctx::ws, ws_get), by owner.
+// A buffer is keyed by its index alone: two functions of one call chain must
+// not take the same one.  Where a number has two names, the owners are entry
+// points (or stages of one) that never run inside one another, and neither
+// keeps the contents across calls.
+enum WsSlot : int {
+	// set operations and (de)serialization (table.hip), the stability filter
+	// (stable.hip); 3 also the per-call triage path's candidates (triage.hip)
+	kWsOp0 = 0,
+	kWsOp1 = 1,
+	kWsOp2 = 2,
+	kWsOp3 = 3,
+	// triage.hip: the per-call path's candidates (with kWsOp3), the batch's prio mask
+	kWsCandMeta = 4,
+	kWsCandCount = 5,
+	kWsPrioMask = 6,
+	// minimize.hip: the host entry's uploads (9 also synth.hip's tile offsets)
+	kWsMinOff = 7,
+	kWsMinElems = 8,
+	kWsMinPrios = 9,
+	kWsSynthTiles = 9,
+	kWsMinKeep = 10,
+	kWsRestoreKeys = 11,  // table.hip: set_restore_keys
+	kWsCallBits = 12,     // triage.hip: per-record bits the caller did not ask for
+	// agg.hip: a batch's (call, element) pairs -- raw, the dedup set, the result
+	// (kept across the runs of a batch); minimize.hip's rank sort outside a batch
+	kWsPairsRaw = 13,
+	kWsMinSortKeys = 13,
+	kWsPairSet = 14,
+	kWsMinRank = 14,
+	kWsPairs = 15,
+	kWsMinSortHist = 15,
+	// agg.hip: one aggregation run
+	kWsAggRecs = 16,      // the partitioned records (capped cells: the dummy lines after them)
+	kWsAggCells = 17,     // the cells' plan and counts (cap_layout), or the counted layout's offsets
+	kWsAggTotals = 18,    // counted layout: per-partition totals and bases
+	kWsAggDistE = 19,     // k_agg's distinct lists (agg_lists) ...
+	kWsAggDistF = 20,
+	kWsAggCnt = 21,       // ... and their region counts
+	kWsAggOvfList = 22,   // agg_hbm_fallback: the overflowed partitions
+	kWsAggHbmTable = 23,  // ... and their HBM table
+	// check_new_signal's uploads (triage.hip) | the NewInput batch's per-key merge (corpus.hip)
+	kWsCnsSigs = 24,
+	kWsNiRecTab = 24,
+	kWsCnsStart = 25,
+	kWsNiKeys = 25,
+	kWsCnsLen = 26,
+	kWsNiBufA = 26,
+	kWsCnsPrio = 27,
+	kWsNiBufB = 27,
+	kWsCnsBits = 28,
+	kWsNiEntries = 28,
+	kWsCnsNew = 29,
+	kWsNiGroupTab = 29,
+	// agg.hip: the HBM fallback's distinct lists (agg_aggregate: behind a copy of the LDS regions)
+	kWsAggDistE2 = 30,
+	kWsAggDistF2 = 31,
+	// agg.hip: the slice-exclusive finalize's deferred lists (fin_args)
+	kWsFinDefer = 32,
+	kWsFinDeferNs = 33,
+	// minimize.hip's virtual batch and shard cursors | corpus.hip's merge state and output
+	kWsMinBatch = 34,
+	kWsNiState = 34,
+	kWsAggHbmCnt = 35,  // agg.hip: the one-sync run's fallback region counts | corpus.hip: merged cover
+	kWsNiCoverOut = 35,
+	kWsMinCursor = 36,
+	kWsNiOut = 36,
+	kWsSuStage2 = 37,  // comps.hip (see kWsSuMeta)
+	kWsNiGroupCover = 38,
+	// manager poll (poll.hip) | the NewInput batch's acceptance and uploads (corpus.hip)
+	kWsPollTargets = 39,
+	kWsPollElems = 40,
+	kWsNiElems = 40,
+	kWsPollPrios = 41,
+	kWsNiPrios = 41,
+	kWsPollGroupIn = 42,
+	kWsNiCover = 42,
+	kWsPollKeys = 43,
+	kWsNiStageA = 43,  // acceptance: the key table, then the commit: the inputs' flags
+	kWsPollEvents = 44,
+	kWsNiStageB = 44,  // acceptance: the sort keys, then the commit: cover offsets
+	kWsNiRecs = 45,
+	kWsPollTable = 46,
+	kWsNiEvents = 46,
+	kWsPollCounts = 47,
+	kWsNiAccepted = 47,
+	// the sort-unique of cover.hip and of the comparison hints (comps.hip, with kWsSuStage2)
+	// | rp_group, the LDS grouping for Poll (recs.hip)
+	kWsSuMeta = 48,
+	kWsRpgSeg = 48,
+	kWsSuTab = 49,
+	kWsRpgKeys = 49,
+	kWsSuBufA = 50,
+	kWsRpgCounts = 50,
+	kWsSuBufB = 51,
+	kWsRpgBase = 51,
+	kWsSuStage = 52,
+	// agg.hip: reserve_slices' histogram, the fast plan's partials | corpus.hip's merge tables
+	kWsPartHist = 53,
+	kWsNiTiles = 53,
+	kWsFastPart = 54,
+	kWsNiItems = 54,
+	// the sharded step (agg.hip, recs.hip) and the LDS records path (recs.hip)
+	kWsStepPairs = 55,
+	kWsRpKeys = 56,
+	kWsRpCounts = 57,
+	kWsRpBase = 58,
+	kWsRpSeg = 59,
+	kWsStepShards = 60,
+	kWsStepRecs = 61,
+	kWsStepFlags = 62,
+	kWsStepCursor = 63,
+	kWsCount = 64,
+};
+
 // the debug flags that change only the path taken, never a result
 constexpr uint32_t kDebugResultPreserving =
     SYZSIG_DEBUG_FIN_DEFER | SYZSIG_DEBUG_MIN_ATOMIC | SYZSIG_DEBUG_EXACT_CELLS | SYZSIG_DEBUG_CAP_SPILL |
     SYZSIG_DEBUG_RECS_GATE | SYZSIG_DEBUG_EDGE_MARKALL | SYZSIG_DEBUG_EDGE_PASSES | SYZSIG_DEBUG_AGG_IDX64;
 // ... and those a product build accepts: the above plus fault injection
 constexpr uint32_t kDebugAccepted = kDebugResultPreserving | SYZSIG_DEBUG_POLL_FAIL;
+// experiment builds only (outside kDebugAccepted): a planned triage run always,
+// finalized by the atomic kernel (no one-sync run, no slice-exclusive finalize)
+constexpr uint32_t kDebugAtomicFinalize = 16u;
 
 // capped cells of the aggregation path (agg.hip): default slack, in standard deviations
 constexpr float kCapSdDefault = 6.0f;
@@ -99,14 +217,8 @@ struct syzsig_ctx {
 	// pinned staging for the small per-batch copies (a pageable copy is staged
 	// and synchronous): syz::kPin* offsets
 	char* h_pin = nullptr;
-	// grow-only scratch buffers by role (35: the one-sync run's fallback): 0-2 set ops, 3-6 triage candidates and
-	// small state, 7-10 host uploads of minimize, 11-14 triage partitions and
-	// minimize internals and triage pairs (13-15), 16-23 + 30-31 triage aggregation, 55-63 the sharded step and
-	// the LDS records path,
-	// 24-29 check_new_signal uploads, 32-33 the finalize's deferred lists, 40-47 manager poll and
-	// the NewInput batch's acceptance (corpus.hip; its per-key merge: 24-29, 34, 36, 38, 53, 54),
-	// 48-52 the cover sort-unique (cover.hip) and, with 37, the comparison hints' (comps.hip)
-	syz::Workspace ws[64];
+	// grow-only scratch buffers, one per syz::WsSlot
+	syz::Workspace ws[syz::kWsCount];
 	bool timing = false;                  // HIP events around triage kernels
 	// tuning knobs (defaults; SYZSIG_* environment overrides read at ctx creation)
 	int part_mode = 1;                    // 0 = never use the aggregation path (agg.hip)

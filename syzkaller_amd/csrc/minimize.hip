@@ -395,7 +395,7 @@ static int minimize_agg_run(syzsig_ctx* ctx, const uint64_t* d_off, const uint32
 	*redo = false;
 	hipStream_t st = ctx->stream;
 	void* vb;
-	SYZ_TRY(ws_get(ctx, 34, nctx * 12 + 128, &vb));
+	SYZ_TRY(ws_get(ctx, kWsMinBatch, nctx * 12 + 128, &vb));
 	uint32_t* dmask = (uint32_t*)vb;                               // [0, 32)
 	uint32_t* dflag = (uint32_t*)((char*)vb + 48);                 // a prio without a level (optimistic run)
 	unsigned long long* dbad = (unsigned long long*)((char*)vb + 56);  // contexts of >= 2^24 entries
@@ -479,7 +479,7 @@ static int minimize_order(syzsig_ctx* ctx, const uint64_t* d_off, uint64_t nctx,
 {
 	hipStream_t st = ctx->stream;
 	void* dk;
-	SYZ_TRY(ws_get(ctx, 13, nctx * 16 + 64, &dk));
+	SYZ_TRY(ws_get(ctx, kWsMinSortKeys, nctx * 16 + 64, &dk));
 	uint32_t* dv = (uint32_t*)dk + nctx;
 	uint32_t* dk2 = dv + nctx;
 	uint32_t* dv2 = dk2 + nctx;
@@ -490,7 +490,7 @@ static int minimize_order(syzsig_ctx* ctx, const uint64_t* d_off, uint64_t nctx,
 	SYZ_HIP(hipStreamSynchronize(st));
 	k_min_keys<<<grid_for(nctx, 256), 256, 0, st>>>(d_off, nctx, maxlen, (uint32_t*)dk, dv);
 	uint32_t *sk, *sv;
-	SYZ_TRY(radix_sort_pairs(ctx, (uint32_t*)dk, dv, dk2, dv2, (uint32_t)nctx, bits_of(maxlen), &sk, &sv, 15));
+	SYZ_TRY(radix_sort_pairs(ctx, (uint32_t*)dk, dv, dk2, dv2, (uint32_t)nctx, bits_of(maxlen), &sk, &sv, kWsMinSortHist));
 	*order = sv;
 	return SYZSIG_OK;
 }
@@ -552,7 +552,7 @@ int syzsig_minimize_split_dev(syzsig_ctx* ctx, const uint64_t* d_off, const uint
 	// the part's contexts as a virtual batch in rank order
 	const uint64_t n = r_hi - r_lo;
 	void* vb;
-	SYZ_TRY(ws_get(ctx, 34, n * 12 + 128, &vb));
+	SYZ_TRY(ws_get(ctx, kWsMinBatch, n * 12 + 128, &vb));
 	uint32_t* dmask = (uint32_t*)vb;
 	uint64_t* cstart = (uint64_t*)((char*)vb + 64);
 	uint32_t* clen = (uint32_t*)(cstart + n);
@@ -583,7 +583,7 @@ int syzsig_minimize_split_dev(syzsig_ctx* ctx, const uint64_t* d_off, const uint
 		syzsig_set* t = nullptr;
 		SYZ_TRY(set_alloc(ctx, buckets_for(local), &t));
 		void* dcur;
-		int rc = ws_get(ctx, 36, 2 * kMinMaxShards * 8, &dcur);
+		int rc = ws_get(ctx, kWsMinCursor, 2 * kMinMaxShards * 8, &dcur);
 		unsigned long long* counts = (unsigned long long*)dcur;
 		unsigned long long* cursor = counts + kMinMaxShards;
 		unsigned long long h[kMinMaxShards] = {};
@@ -635,7 +635,7 @@ int syzsig_minimize_split_dev(syzsig_ctx* ctx, const uint64_t* d_off, const uint
 	AggOut a;
 	SYZ_TRY(agg_aggregate(ctx, &b, 0, n, lm, local, &bst, &a, &x));
 	void* dcur;
-	SYZ_TRY(ws_get(ctx, 36, 2 * kMinMaxShards * 8, &dcur));
+	SYZ_TRY(ws_get(ctx, kWsMinCursor, 2 * kMinMaxShards * 8, &dcur));
 	unsigned long long* counts = (unsigned long long*)dcur;
 	unsigned long long* cursor = counts + kMinMaxShards;
 	SYZ_HIP(hipMemsetAsync(counts, 0, kMinMaxShards * 8, st));
@@ -711,11 +711,11 @@ int syzsig_minimize_shard_dev(syzsig_ctx* ctx, const uint64_t* d_off, const uint
 		return fail(SYZSIG_ERANGE, "minimize: more than 2^24-2 contexts");
 	hipStream_t st = ctx->stream;
 	void *dk, *dv, *dk2, *dv2, *drank;
-	SYZ_TRY(ws_get(ctx, 13, nctx * 16 + 64, &dk));
+	SYZ_TRY(ws_get(ctx, kWsMinSortKeys, nctx * 16 + 64, &dk));
 	dv = (uint32_t*)dk + nctx;
 	dk2 = (uint32_t*)dv + nctx;
 	dv2 = (uint32_t*)dk2 + nctx;
-	SYZ_TRY(ws_get(ctx, 14, nctx * 4 + 64, &drank));
+	SYZ_TRY(ws_get(ctx, kWsMinRank, nctx * 4 + 64, &drank));
 	// the entry count and the longest context (the order's sort passes), one sync
 	uint64_t total = 0;
 	uint32_t maxlen = 0;
@@ -732,7 +732,7 @@ int syzsig_minimize_shard_dev(syzsig_ctx* ctx, const uint64_t* d_off, const uint
 	k_min_keys<<<grid_for(nctx, 256), 256, 0, st>>>(d_off, nctx, maxlen, (uint32_t*)dk, (uint32_t*)dv);
 	uint32_t *sk, *sv;
 	SYZ_TRY(radix_sort_pairs(ctx, (uint32_t*)dk, (uint32_t*)dv, (uint32_t*)dk2, (uint32_t*)dv2, (uint32_t)nctx,
-	                         bits_of(maxlen), &sk, &sv, 15));
+	                         bits_of(maxlen), &sk, &sv, kWsMinSortHist));
 	const uint32_t* order = sv;
 	bool used = false;
 	if (total && !(ctx->agg_dbg & SYZSIG_DEBUG_MIN_ATOMIC))
@@ -811,10 +811,10 @@ int syzsig_minimize(syzsig_ctx* ctx, const uint64_t* ctx_off, const uint32_t* el
 	if (ctx_off[0] != 0)
 		return fail(SYZSIG_EINVAL, "minimize: ctx_off[0] must be 0");
 	void *doff, *de, *dp, *dkeep;
-	SYZ_TRY(ws_get(ctx, 7, (nctx + 1) * 8, &doff));
-	SYZ_TRY(ws_get(ctx, 8, total * 4 + 4, &de));
-	SYZ_TRY(ws_get(ctx, 9, total + 1, &dp));
-	SYZ_TRY(ws_get(ctx, 10, nctx + 1, &dkeep));
+	SYZ_TRY(ws_get(ctx, kWsMinOff, (nctx + 1) * 8, &doff));
+	SYZ_TRY(ws_get(ctx, kWsMinElems, total * 4 + 4, &de));
+	SYZ_TRY(ws_get(ctx, kWsMinPrios, total + 1, &dp));
+	SYZ_TRY(ws_get(ctx, kWsMinKeep, nctx + 1, &dkeep));
 	SYZ_HIP(hipMemcpyAsync(doff, ctx_off, (nctx + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
 	if (total) {
 		SYZ_HIP(hipMemcpyAsync(de, elems, total * 4, hipMemcpyHostToDevice, ctx->stream));

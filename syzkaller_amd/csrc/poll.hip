@@ -437,12 +437,12 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 	SYZ_TRY(set_reserve(ms, n));  // (a growth keeps the contents)
 	// uploads and scratch: entries, their grouping input, events, the target table
 	void *de, *dp, *drp, *dx, *dev, *dnext;
-	SYZ_TRY(ws_get(ctx, 40, n * 4 + 64, &de));
-	SYZ_TRY(ws_get(ctx, 41, n + 64, &dp));
-	SYZ_TRY(ws_get(ctx, 42, n * 4 + ((uint64_t)K + 1) * 8 + 64, &drp));
+	SYZ_TRY(ws_get(ctx, kWsPollElems, n * 4 + 64, &de));
+	SYZ_TRY(ws_get(ctx, kWsPollPrios, n + 64, &dp));
+	SYZ_TRY(ws_get(ctx, kWsPollGroupIn, n * 4 + ((uint64_t)K + 1) * 8 + 64, &drp));
 	uint64_t* doff = (uint64_t*)((uint32_t*)drp + ((n + 1) & ~1ull));
-	SYZ_TRY(ws_get(ctx, 43, n * 8 + 64, &dx));
-	SYZ_TRY(ws_get(ctx, 44, n * 8 + ((uint64_t)K * F + K) * 4 + 64, &dev));
+	SYZ_TRY(ws_get(ctx, kWsPollKeys, n * 8 + 64, &dx));
+	SYZ_TRY(ws_get(ctx, kWsPollEvents, n * 8 + ((uint64_t)K * F + K) * 4 + 64, &dev));
 	dnext = (uint64_t*)dev + n;
 	uint32_t* dpf = (uint32_t*)dnext + (uint64_t)K * F;
 	if (ctx->timing)  // (the call's stream work from its uploads to its last kernel: ctx last_ms)
@@ -487,8 +487,8 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 			entries += syzsig_len(new_max[g]);
 	const uint64_t C = pow2_ge(std::max<uint64_t>(2 * entries, 1024));
 	void *dT, *dtc;
-	SYZ_TRY(ws_get(ctx, 46, C * 8 + 64, &dT));
-	SYZ_TRY(ws_get(ctx, 47, ((uint64_t)K + F) * 8 + 64, &dtc));
+	SYZ_TRY(ws_get(ctx, kWsPollTable, C * 8 + 64, &dT));
+	SYZ_TRY(ws_get(ctx, kWsPollCounts, ((uint64_t)K + F) * 8 + 64, &dtc));
 	unsigned int* tcount = (unsigned int*)dtc;
 	unsigned int* tins = tcount + K + F;
 	SYZ_HIP(hipMemsetAsync(dT, 0xff, C * 8, s));
@@ -524,7 +524,7 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 		tg[t] = PollTarget{tset[t]->slots, tset[t]->nbuckets - 1};
 	}
 	void* dtg;
-	SYZ_TRY(ws_get(ctx, 39, ((uint64_t)K + F) * sizeof(PollTarget) + 64, &dtg));
+	SYZ_TRY(ws_get(ctx, kWsPollTargets, ((uint64_t)K + F) * sizeof(PollTarget) + 64, &dtg));
 	SYZ_HIP(hipMemcpyAsync(dtg, tg.data(), ((uint64_t)K + F) * sizeof(PollTarget), hipMemcpyHostToDevice, s));
 	// ---- commit: maxSignal.Merge of the events, the targets filled ----
 	// (the event count is passed by value: the counter reset clears *nev)

@@ -539,9 +539,9 @@ int rp_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set* nsp, const RpSrc& src0, 
 	// per bound record: key 8 + index 4 + its element's index 4 + (as elements)
 	// element 4 + firsts 16 + M0 2
 	const uint64_t nb = (bound + 3) & ~3ull;  // array strides: the firsts stay 16-B aligned
-	SYZ_TRY(ws_get(ctx, 56, nb * 38 + 1024, &wk));
-	SYZ_TRY(ws_get(ctx, 57, ntiles * P * 4 + 256, &wc));
-	SYZ_TRY(ws_get(ctx, 58, (uint64_t)(kRpGroups + 3 + kRpNumCnt) * P * 4 + 256, &wb));
+	SYZ_TRY(ws_get(ctx, kWsRpKeys, nb * 38 + 1024, &wk));
+	SYZ_TRY(ws_get(ctx, kWsRpCounts, ntiles * P * 4 + 256, &wc));
+	SYZ_TRY(ws_get(ctx, kWsRpBase, (uint64_t)(kRpGroups + 3 + kRpNumCnt) * P * 4 + 256, &wb));
 	uint64_t* keys = (uint64_t*)wk;
 	uint4* ef = (uint4*)(keys + nb);
 	uint32_t* idx = (uint32_t*)(ef + nb);
@@ -617,16 +617,16 @@ int rp_group(syzsig_ctx* ctx, const uint64_t* x, uint64_t n, uint64_t** keys_out
 	if (n >= (1ull << 32))
 		return fail(SYZSIG_ERANGE, "group: 2^32 entries or more");
 	void *wseg, *wk, *wc, *wb;
-	SYZ_TRY(ws_get(ctx, 48, 64, &wseg));
+	SYZ_TRY(ws_get(ctx, kWsRpgSeg, 64, &wseg));
 	RpSrc src{x, n, 0, 1, (const uint64_t*)wseg, 0, 0};
 	const uint64_t tile = std::max<uint64_t>(kRpTileMin, (n / 1024 + 4095) & ~4095ull);
 	src.tile = (uint32_t)tile;
 	src.tiles_per_seg = (uint32_t)std::max<uint64_t>(1, (n + tile - 1) / tile);
 	const uint64_t ntiles = src.tiles_per_seg;
 	const uint32_t pbits = rp_pbits(n), P = 1u << pbits;
-	SYZ_TRY(ws_get(ctx, 49, n * 8 + 64, &wk));
-	SYZ_TRY(ws_get(ctx, 50, ntiles * P * 4 + 256, &wc));
-	SYZ_TRY(ws_get(ctx, 51, (uint64_t)(kRpGroups + 3) * P * 4 + 256, &wb));
+	SYZ_TRY(ws_get(ctx, kWsRpgKeys, n * 8 + 64, &wk));
+	SYZ_TRY(ws_get(ctx, kWsRpgCounts, ntiles * P * 4 + 256, &wc));
+	SYZ_TRY(ws_get(ctx, kWsRpgBase, (uint64_t)(kRpGroups + 3) * P * 4 + 256, &wb));
 	uint32_t* cnt = (uint32_t*)wc;
 	uint32_t* tot = (uint32_t*)wb;
 	uint32_t* base = tot + P;       // P + 1 entries
@@ -658,7 +658,7 @@ int rp_triage_records(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const ui
 	syzsig_set* nsp = *ns;
 	SYZ_TRY(set_reserve_load(nsp, nrec, kHardLoad));
 	void* ws;
-	SYZ_TRY(ws_get(ctx, 59, 64, &ws));
+	SYZ_TRY(ws_get(ctx, kWsRpSeg, 64, &ws));
 	const hipStream_t s = ctx->stream;
 	k_rp_one_seg<<<1, 64, 0, s>>>((uint64_t*)ws, nrec, ctx->d_cnt);
 	const RpSrc src{recs, nrec, 0, 1, (const uint64_t*)ws, 0, 0};
@@ -735,7 +735,7 @@ int syzsig_step_own_dev(syzsig_ctx* ctx, syzsig_set* shard, syzsig_set* new_sign
 	const hipStream_t s = ctx->stream;
 	unsigned long long* oc = ctx->d_step + kStepOwn;
 	void* wsg;
-	SYZ_TRY(ws_get(ctx, 60, (uint64_t)nshards * 16 + 64, &wsg));
+	SYZ_TRY(ws_get(ctx, kWsStepShards, (uint64_t)nshards * 16 + 64, &wsg));
 	uint64_t* seg_cnt = (uint64_t*)wsg;
 	uint64_t* seg_off = seg_cnt + nshards;
 	ctx->step_own_timed = ctx->timing;
@@ -775,8 +775,8 @@ int syzsig_step_own_dev(syzsig_ctx* ctx, syzsig_set* shard, syzsig_set* new_sign
 				memset(&st, 0, sizeof(st));
 				if (n) {
 					void *wr, *wf;
-					SYZ_TRY(ws_get(ctx, 61, n * 16 + 64, &wr));
-					SYZ_TRY(ws_get(ctx, 62, n + 64, &wf));
+					SYZ_TRY(ws_get(ctx, kWsStepRecs, n * 16 + 64, &wr));
+					SYZ_TRY(ws_get(ctx, kWsStepFlags, n + 64, &wf));
 					uint64_t* comp = (uint64_t*)wr;
 					uint64_t* slot = comp + n;
 					SYZ_HIP(hipMemcpyAsync(seg_off, off.data(), nshards * 8, hipMemcpyHostToDevice, s));

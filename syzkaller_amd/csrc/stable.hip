@@ -228,10 +228,10 @@ extern "C" int syzsig_triage_runs_dev(syzsig_ctx* ctx, const uint64_t* d_item_of
 		return fail(SYZSIG_ERANGE, "triage_runs: too many runs");
 	const uint64_t C = pow2_ge(std::max<uint64_t>(2 * nsig + 16, 64));
 	void *set, *alive, *cnt, *stop;
-	SYZ_TRY(ws_get(ctx, 0, C * 8, &set));
-	SYZ_TRY(ws_get(ctx, 1, nelem + 64, &alive));
-	SYZ_TRY(ws_get(ctx, 2, nruns * 8 + 64, &cnt));
-	SYZ_TRY(ws_get(ctx, 3, nitems + 64, &stop));
+	SYZ_TRY(ws_get(ctx, kWsOp0, C * 8, &set));
+	SYZ_TRY(ws_get(ctx, kWsOp1, nelem + 64, &alive));
+	SYZ_TRY(ws_get(ctx, kWsOp2, nruns * 8 + 64, &cnt));
+	SYZ_TRY(ws_get(ctx, kWsOp3, nitems + 64, &stop));
 	SYZ_HIP(hipMemsetAsync(set, 0xff, C * 8, s));
 	SYZ_HIP(hipMemsetAsync(cnt, 0, nruns * 8 + 8, s));
 	if (nsig)
@@ -279,9 +279,9 @@ extern "C" int syzsig_minimize_pred_dev(syzsig_ctx* ctx, const uint64_t* d_item_
 		return fail(SYZSIG_ERANGE, "minimize_pred: too many runs");
 	const uint64_t C = pow2_ge(std::max<uint64_t>(2 * nsig + 16, 64));
 	void *set, *alive, *cnt;
-	SYZ_TRY(ws_get(ctx, 0, C * 8, &set));
-	SYZ_TRY(ws_get(ctx, 1, nelem + 64, &alive));
-	SYZ_TRY(ws_get(ctx, 2, nruns * 8 + 64, &cnt));
+	SYZ_TRY(ws_get(ctx, kWsOp0, C * 8, &set));
+	SYZ_TRY(ws_get(ctx, kWsOp1, nelem + 64, &alive));
+	SYZ_TRY(ws_get(ctx, kWsOp2, nruns * 8 + 64, &cnt));
 	SYZ_HIP(hipMemsetAsync(set, 0xff, C * 8, s));
 	SYZ_HIP(hipMemsetAsync(cnt, 0, nruns * 8 + 8, s));
 	if (nsig)

@@ -238,7 +238,7 @@ int syzsig_synth_m0_shard_dev(syzsig_ctx* ctx, const syzsig_synth_cfg* cfg, uint
 	if (ntiles > 0x7FFFFFFFull)
 		return fail(SYZSIG_ERANGE, "synth_m0_shard: n too large");
 	void* w;
-	SYZ_TRY(ws_get(ctx, 9, (ntiles + 1) * 8 + 64, &w));
+	SYZ_TRY(ws_get(ctx, kWsSynthTiles, (ntiles + 1) * 8 + 64, &w));
 	uint64_t* tcnt = (uint64_t*)w;
 	uint64_t* tot = tcnt + ntiles;
 	const hipStream_t st = ctx->stream;

@@ -637,7 +637,7 @@ int syzsig_set_restore_keys(syzsig_ctx* ctx, syzsig_set* dst, const syzsig_set* 
 		return fail(SYZSIG_EINVAL, "set_restore_keys: capacity mismatch (dst grew since the snapshot)");
 	if (keys && keys->len) {
 		void* ib;
-		SYZ_TRY(ws_get(ctx, 11, keys->nslots() * 8 + 64, &ib));
+		SYZ_TRY(ws_get(ctx, kWsRestoreKeys, keys->nslots() * 8 + 64, &ib));
 		const int g = grid_for(keys->nslots(), 256, 8192);
 		k_restore_find<<<g, 256, 0, ctx->stream>>>(dst->slots, dst->nbuckets - 1, keys->slots, keys->nslots(),
 		                                           (int64_t*)ib);
@@ -699,7 +699,7 @@ int syzsig_from_raw(syzsig_ctx* ctx, const uint32_t* raw, uint64_t n, uint8_t pr
 	if (n == 0)
 		return SYZSIG_OK;  // signal.go:32-34
 	void* d = nullptr;
-	SYZ_TRY(upload(ctx, 0, raw, n * 4, &d));
+	SYZ_TRY(upload(ctx, kWsOp0, raw, n * 4, &d));
 	return make_result(ctx, n, false, out, [&](syzsig_set* r) {
 		k_from_raw<<<grid_for(n, 256), 256, 0, ctx->stream>>>(r->slots, r->nbuckets - 1, (const uint32_t*)d, n,
 		                                                       (int8_t)prio, ctx->d_cnt);
@@ -721,8 +721,8 @@ int syzsig_serialize(syzsig_ctx* ctx, const syzsig_set* s, uint32_t* elems, int8
 	uint64_t chunk = (nslots + nblk - 1) / nblk;
 	uint64_t m = std::min<uint64_t>(cap, s->len);
 	void *d_counts, *d_out;
-	SYZ_TRY(ws_get(ctx, 1, (nblk + 1) * sizeof(unsigned long long), &d_counts));
-	SYZ_TRY(ws_get(ctx, 2, m * 5 + 16, &d_out));
+	SYZ_TRY(ws_get(ctx, kWsOp1, (nblk + 1) * sizeof(unsigned long long), &d_counts));
+	SYZ_TRY(ws_get(ctx, kWsOp2, m * 5 + 16, &d_out));
 	unsigned long long* counts = (unsigned long long*)d_counts;
 	k_count_live<<<nblk, 256, 0, ctx->stream>>>(s->slots, nslots, chunk, counts);
 	k_scan_counts<<<1, 1024, 0, ctx->stream>>>(counts, nblk, counts + nblk);
@@ -772,10 +772,10 @@ int syzsig_serialize_batch(syzsig_ctx* ctx, const syzsig_set* const* sets, uint6
 	if (nb >= (1u << 31))
 		return fail(SYZSIG_ERANGE, "serialize_batch: too many sets");
 	void *d_desc, *d_blk, *d_counts, *d_out;
-	SYZ_TRY(ws_get(ctx, 0, desc.size() * sizeof(SerDesc), &d_desc));
-	SYZ_TRY(ws_get(ctx, 1, (nb + 1) * sizeof(unsigned long long), &d_counts));
-	SYZ_TRY(ws_get(ctx, 2, total * 5 + 16, &d_out));
-	SYZ_TRY(ws_get(ctx, 3, nb * sizeof(uint32_t), &d_blk));
+	SYZ_TRY(ws_get(ctx, kWsOp0, desc.size() * sizeof(SerDesc), &d_desc));
+	SYZ_TRY(ws_get(ctx, kWsOp1, (nb + 1) * sizeof(unsigned long long), &d_counts));
+	SYZ_TRY(ws_get(ctx, kWsOp2, total * 5 + 16, &d_out));
+	SYZ_TRY(ws_get(ctx, kWsOp3, nb * sizeof(uint32_t), &d_blk));
 	SYZ_HIP(hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(SerDesc), hipMemcpyHostToDevice, ctx->stream));
 	SYZ_HIP(hipMemcpyAsync(d_blk, blk_set.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 	unsigned long long* counts = (unsigned long long*)d_counts;
@@ -823,8 +823,8 @@ int syzsig_deserialize(syzsig_ctx* ctx, const uint32_t* elems, uint64_t n_elems,
 	if (!elems || !prios)
 		return fail(SYZSIG_EINVAL, "deserialize: NULL argument");
 	void *de, *dp;
-	SYZ_TRY(upload(ctx, 0, elems, n_elems * 4, &de));
-	SYZ_TRY(upload(ctx, 1, prios, n_elems, &dp));
+	SYZ_TRY(upload(ctx, kWsOp0, elems, n_elems * 4, &de));
+	SYZ_TRY(upload(ctx, kWsOp1, prios, n_elems, &dp));
 	return syzsig_deserialize_dev(ctx, (const uint32_t*)de, (const int8_t*)dp, n_elems, out);
 }
 
@@ -857,7 +857,7 @@ int syzsig_diff_raw(syzsig_ctx* ctx, const syzsig_set* s, const uint32_t* raw, u
 	if (n == 0)
 		return SYZSIG_OK;
 	void* d = nullptr;
-	SYZ_TRY(upload(ctx, 0, raw, n * 4, &d));
+	SYZ_TRY(upload(ctx, kWsOp0, raw, n * 4, &d));
 	bool have = s && s->len;
 	return make_result(ctx, n, true, out, [&](syzsig_set* r) {
 		k_diff_raw<<<grid_for(n, 256), 256, 0, ctx->stream>>>(have ? s->slots : nullptr, have ? s->nbuckets - 1 : 0,
@@ -911,7 +911,7 @@ int syzsig_cover_merge(syzsig_ctx* ctx, syzsig_set** cov, const uint32_t* raw, u
 	if (!ctx || !cov || (n && !raw))
 		return fail(SYZSIG_EINVAL, "cover_merge: NULL argument");
 	void* d = nullptr;
-	SYZ_TRY(upload(ctx, 0, raw, n * 4, &d));
+	SYZ_TRY(upload(ctx, kWsOp0, raw, n * 4, &d));
 	return cover_merge_dev(ctx, cov, (const uint32_t*)d, n);
 }
 

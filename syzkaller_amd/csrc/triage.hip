@@ -449,7 +449,7 @@ static void level_map_from(const bool present[256], LevelMap* lm)
 int batch_total_records(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t* total, uint32_t prio_mask[8])
 {
 	void* dmask;
-	SYZ_TRY(ws_get(ctx, 6, 64, &dmask));
+	SYZ_TRY(ws_get(ctx, kWsPrioMask, 64, &dmask));
 	SYZ_HIP(hipMemsetAsync(dmask, 0, 48, ctx->stream));
 	k_prio_presence<<<grid_for(b->ncalls, 256, 256), 256, 0, ctx->stream>>>(
 	    b->call_prio, b->call_len, b->call_start, b->ncalls, b->nrec, (uint32_t*)dmask,
@@ -647,7 +647,7 @@ int triage_batch_impl(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const sy
 		uint32_t* bits = b->new_bits;
 		if (!bits) {
 			void* ib;
-			SYZ_TRY(ws_get(ctx, 12, ((b->nrec + 31) / 32) * 4 + 64, &ib));
+			SYZ_TRY(ws_get(ctx, kWsCallBits, ((b->nrec + 31) / 32) * 4 + 64, &ib));
 			bits = (uint32_t*)ib;
 			SYZ_HIP(hipMemsetAsync(bits, 0, ((b->nrec + 31) / 32) * 4, ctx->stream));
 		}
@@ -662,9 +662,9 @@ int triage_batch_impl(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const sy
 		in.new_bits = bits;
 		in.call_new = b->call_new;
 		void *cs, *cm, *cc;
-		SYZ_TRY(ws_get(ctx, 3, b->nrec * 4, &cs));
-		SYZ_TRY(ws_get(ctx, 4, b->nrec * 4, &cm));
-		SYZ_TRY(ws_get(ctx, 5, maxrun * 4, &cc));
+		SYZ_TRY(ws_get(ctx, kWsOp3, b->nrec * 4, &cs));
+		SYZ_TRY(ws_get(ctx, kWsCandMeta, b->nrec * 4, &cm));
+		SYZ_TRY(ws_get(ctx, kWsCandCount, maxrun * 4, &cc));
 		auto prep = [&](CallsIn* cin, int* grid, syzsig_batch_stats*) -> int {
 			*cin = in;
 			*grid = grid_for((r.c1 - r.c0) * 64, 256, 4096);
@@ -728,9 +728,9 @@ int triage_records_impl(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const 
 	SYZ_TRY(set_ensure_triage_state(ms));
 	const uint64_t nseg = (nrec + kSegRecs - 1) / kSegRecs;
 	void *cs, *cm, *cc;
-	SYZ_TRY(ws_get(ctx, 3, nrec * 4, &cs));
-	SYZ_TRY(ws_get(ctx, 4, nrec * 4, &cm));
-	SYZ_TRY(ws_get(ctx, 5, nseg * 4, &cc));
+	SYZ_TRY(ws_get(ctx, kWsOp3, nrec * 4, &cs));
+	SYZ_TRY(ws_get(ctx, kWsCandMeta, nrec * 4, &cm));
+	SYZ_TRY(ws_get(ctx, kWsCandCount, nseg * 4, &cc));
 	auto prep = [&](RecsIn* in, int* grid, syzsig_batch_stats*) -> int {
 		in->recs = recs;
 		in->nrec = nrec;
@@ -792,12 +792,12 @@ int syzsig_check_new_signal(syzsig_ctx* ctx, syzsig_set** max_signal, syzsig_set
 		SYZ_TRY(syzsig_set_make(ctx, 0, max_signal));
 	const uint64_t nwords = (nrec + 31) / 32;
 	void *ds, *dcs, *dcl, *dcp, *dbits, *dnew;
-	SYZ_TRY(ws_get(ctx, 24, nrec * 4 + 4, &ds));
-	SYZ_TRY(ws_get(ctx, 25, ncalls * 8 + 8, &dcs));
-	SYZ_TRY(ws_get(ctx, 26, ncalls * 4 + 4, &dcl));
-	SYZ_TRY(ws_get(ctx, 27, ncalls + 1, &dcp));
-	SYZ_TRY(ws_get(ctx, 28, nwords * 4 + 4, &dbits));
-	SYZ_TRY(ws_get(ctx, 29, ncalls + 1, &dnew));
+	SYZ_TRY(ws_get(ctx, kWsCnsSigs, nrec * 4 + 4, &ds));
+	SYZ_TRY(ws_get(ctx, kWsCnsStart, ncalls * 8 + 8, &dcs));
+	SYZ_TRY(ws_get(ctx, kWsCnsLen, ncalls * 4 + 4, &dcl));
+	SYZ_TRY(ws_get(ctx, kWsCnsPrio, ncalls + 1, &dcp));
+	SYZ_TRY(ws_get(ctx, kWsCnsBits, nwords * 4 + 4, &dbits));
+	SYZ_TRY(ws_get(ctx, kWsCnsNew, ncalls + 1, &dnew));
 	if (nrec)
 		SYZ_HIP(hipMemcpyAsync(ds, sigs, nrec * 4, hipMemcpyHostToDevice, ctx->stream));
 	if (ncalls) {
