@@ -46,7 +46,7 @@ namespace syz {
 // Device counters live in one small array per context (zeroed per operation).
 enum Counter : int {
 	kCntInserted = 0,   // new keys inserted into the destination table
-	kCntOverflow,       // probe limit hit (capacity too small) -> retry bigger
+	kCntOverflow,       // an insert found the whole table occupied (capacity too small) -> retry bigger
 	kCntError,          // malformed input detected on device
 	kCntCandidates,     // triage: records that passed the prio filter
 	kCntTouched,        // triage: distinct elements with a candidate this run
@@ -371,7 +371,6 @@ int pairs_from_bits(syzsig_ctx* ctx, const syzsig_batch* b, const uint32_t* bits
 constexpr double kMaxLoad = 0.75;
 constexpr double kTargetLoad = 0.5;
 constexpr double kHardLoad = 0.9;  // a reservation for a worst case grows the table only past this
-constexpr uint32_t kMaxProbeBuckets = 4096;
 
 inline int grid_for(uint64_t n, int block, int max_blocks = 2048)
 {
@@ -557,10 +556,13 @@ __device__ __forceinline__ int64_t tbl_find_or_insert_from(uint64_t* slots, uint
 	return -1;
 }
 
+// Probe bound of an insert: the whole table.  The set operations reserve room
+// first (set_reserve*: below load 1), so an empty slot exists and an insert
+// cannot fail however long its chain is -- also when every key shares one home
+// bucket; the triage probe path restarts on a bigger table when its table fills.
 __device__ __forceinline__ uint64_t max_probe_for(uint64_t bmask)
 {
-	uint64_t nb = bmask + 1;
-	return nb < kMaxProbeBuckets ? nb : kMaxProbeBuckets;  // (kMaxProbeBuckets * kBucketSlots slots)
+	return bmask + 1;
 }
 
 // Insert-or-max (Merge rule).  Returns 1 if inserted, 0 otherwise; -1 overflow.

@@ -1,11 +1,11 @@
 // table.hip -- device-resident Signal (pkg/signal/signal.go) and its algebra.
 //
 // A Signal is an open-addressed table of u64 slots (encoding: common.h) in
-// 64-B buckets of 8 slots, probed bucket-linearly from fmix32(elem).  Every
+// 16-B buckets of 2 slots, probed bucket-linearly from fmix32(elem).  Every
 // operation is one or two grid-stride kernels on the context stream; results
-// are sized from the operation's bound (len(s1), len(raw), ...) so inserts
-// never overflow, and the live count comes back through a block-aggregated
-// device counter.
+// are sized from the operation's bound (len(s1), len(raw), ...) and an insert
+// probes the whole table (max_probe_for), so inserts never overflow, and the
+// live count comes back through a block-aggregated device counter.
 #include <algorithm>
 
 #include "internal.h"

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.table_keys import fmix32_inv_np
 
 pytestmark = pytest.mark.gpu
 
@@ -251,17 +252,6 @@ def test_triage_cell_layouts(gpu, mode):
         gpu.eng.set_debug(0)
     assert st["parts"] >= 8 and st["overflow_parts"] == 0, st
     assert st["retries"] == (1 if mode == "spill" else 0), st
-
-
-def fmix32_inv_np(h):
-    """Inverse of murmur3 fmix32 (csrc/agg.hip fmix32_inv), on a u32 array."""
-    h = np.asarray(h, np.uint32).copy()
-    h ^= h >> np.uint32(16)
-    h *= np.uint32(0x7ED1B41D)
-    h ^= (h >> np.uint32(13)) ^ (h >> np.uint32(26))
-    h *= np.uint32(0xA5CB9243)
-    h ^= h >> np.uint32(16)
-    return h
 
 
 @pytest.mark.parametrize("over", [(0,) * 8, (1, 0, 0, 1, 0, 1, 1, 0), (1,) * 8])
