@@ -27,7 +27,14 @@
 //
 // Pipeline (one run of <= 4 prio levels):
 //   k_agg_count / k_agg_scan_chunks / k_agg_scan_totals / k_agg_scatter
-//       records -> 4-B packed records grouped by partition, cells in chunk order.
+//       records -> 4-B packed records grouped by partition, cells in chunk order
+//       (counted cells: sized by a count pass and a scan).
+//   k_fast_prep or k_chunk_sizes / k_cell_plan / k_scat3 + k_agg_scatter_blk
+//       the same records into capped cells, sized from the chunks' record
+//       counts alone (the default; a cell that overflows voids the run, which
+//       is redone with counted cells).  Both kernels write whole 64/128-B
+//       blocks through ScatBlocks and split the run's work items by how well
+//       k_scat3's one-call tiles would be filled (launch_capped_scatter).
 //   k_agg       one 1024-thread workgroup per partition: an LDS hash table
 //       (residual key + 4 level firsts, 20 B/slot, kAggSlots slots = 145 KiB)
 //       absorbs the partition's records -- one ds_read_b128 of the home bucket,
@@ -43,7 +50,6 @@
 //       from the exact distinct count, so nothing is ever retried.
 //   k_pairs_mark (optional) per-record new bits from the pairs.
 #include <algorithm>
-#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -53,12 +59,8 @@ namespace syz {
 
 constexpr uint32_t kAggThreads = 1024;
 constexpr uint32_t kAggSlots = 7424;               // LDS slots per workgroup (+ 8 KB of first-sight queues)
-// keys per LDS bucket: 4 (one ds_read_b128 per probe) or 2 (ds_read_b64)
-#ifndef SYZ_AGG_BW
-#define SYZ_AGG_BW 4
-#endif
-constexpr uint32_t kAggBW = SYZ_AGG_BW;
-using KBucket = std::conditional_t<kAggBW == 4, uint4, uint2>;
+constexpr uint32_t kAggBW = 4;                     // keys per LDS bucket: one ds_read_b128 per probe
+using KBucket = uint4;
 constexpr uint32_t kAggBuckets = kAggSlots / kAggBW;
 constexpr uint32_t kAggNoSlot = 0xFFFFFFFFu;
 static_assert(kAggRegion == kAggSlots, "distinct-list region per partition (internal.h)");
@@ -66,30 +68,16 @@ constexpr uint32_t kAggLimit = kAggSlots * 4 / 5;  // distinct elements before a
 static_assert(kAggLimit == kAggLimitRecs, "internal.h mirror");
 constexpr double kAggTargetLoad = 0.4;             // partitions are sized for this LDS load
 constexpr double kAggTargetLoadEntry = 0.6;        // ... and for Minimize
-#ifndef SYZ_MIN_ITEMS
-#define SYZ_MIN_ITEMS 2048  // Minimize: at least this many partitioning work items
-#endif
+constexpr uint64_t kMinItems = 2048;               // Minimize: at least this many partitioning work items
 constexpr uint32_t kAggEmpty = 0xFFFFFFFFu;        // empty key (LDS keys are residuals < 2^29)
 constexpr uint32_t kAggNone = 0xFFFFFFFFu;         // no record at this level
 constexpr uint32_t kAggOverflow = 0xFFFFFFFFu;     // partition count marker
 constexpr uint32_t kAggMinBits = 3, kAggMaxBits = 11;
 constexpr uint32_t kAggMaxParts = 1u << kAggMaxBits;
 constexpr uint32_t kAggTile = 18432;  // records per scatter tile (18 per lane; 6 B of LDS each)
-#ifndef SYZ_AGG_GROUP
-#define SYZ_AGG_GROUP 8
-#endif
-constexpr uint32_t kAggGroup = SYZ_AGG_GROUP;  // cells per wave work item of k_agg (<= 64)
+constexpr uint32_t kAggGroup = 8;  // cells per wave work item of k_agg (<= 64)
 // k_agg's record pipeline: U records per lane per batch, D batches in flight ahead
-#ifndef SYZ_AGG_U
-#define SYZ_AGG_U 4
-#endif
-#ifndef SYZ_AGG_D
-#define SYZ_AGG_D 2
-#endif
-constexpr uint32_t kAggU = SYZ_AGG_U, kAggD = SYZ_AGG_D;
-#ifndef SYZ_AGG_OVF_EACH  // k_agg tests its overflow flag after every batch (1) or per group of cells (0)
-#define SYZ_AGG_OVF_EACH 0
-#endif
+constexpr uint32_t kAggU = 4, kAggD = 2;
 
 // Partition geometry of one run (see the header).
 struct AggGeom {
@@ -132,19 +120,11 @@ __device__ __forceinline__ uint32_t bucket_find(uint4 B, uint32_t e)
 {
 	return B.x == e ? 0 : B.y == e ? 1 : B.z == e ? 2 : B.w == e ? 3 : 4;
 }
-__device__ __forceinline__ uint32_t bucket_find(uint2 B, uint32_t e)
-{
-	return B.x == e ? 0 : B.y == e ? 1 : kAggBW;
-}
 
 // position of the first empty key in a 4-key bucket, 4 if full
 __device__ __forceinline__ uint32_t bucket_first_empty(uint4 B)
 {
 	return B.x == kAggEmpty ? 0 : B.y == kAggEmpty ? 1 : B.z == kAggEmpty ? 2 : B.w == kAggEmpty ? 3 : 4;
-}
-__device__ __forceinline__ uint32_t bucket_first_empty(uint2 B)
-{
-	return B.x == kAggEmpty ? 0 : B.y == kAggEmpty ? 1 : kAggBW;
 }
 
 // Find-or-insert e in the LDS key buckets, bucket-linear from its home bucket
@@ -333,18 +313,28 @@ __global__ __launch_bounds__(1024) void k_agg_scan_totals(const uint64_t* totals
 		rec_base[P] = tot;
 }
 
-// Records of each chunk -> their cells (fixed by the scan, so no global
-// atomics).  A tile of kAggTile records lives in registers (kPer per lane),
-// is counting-sorted by partition into LDS and written out as one run per
-// partition; the runs of one chunk's consecutive tiles continue each other.
-// The next tile's loads are issued before the write-out of the current one,
-// so HBM reads overlap the stores instead of following them.
-// kEntry (Minimize): the level comes from each record's own prio
-// (x.elem_prio, parallel to sigs) instead of its call's, and only the records
-// whose element shard x.shard owns are kept.
+// ---------------------------------------------------------------- scatter
+// Three kernels move a run's records into their cells, every one with
+// workgroups of kAggThreads threads that take work items of 2^ibits calls:
+//   k_agg_scatter      counted cells (offsets from the scan), a sorted tile
+//   k_agg_scatter_blk  capped cells, a wave's tile spans calls
+//   k_scat3            capped cells, a wave's tile is a piece of one call
+// The two capped scatters write through ScatBlocks and share a run's work
+// items between them (CapCells::split).
 constexpr uint32_t kScatChunkMax = 1u << (kAggMaxBits - 2);  // calls per chunk (cbits <= 9)
+constexpr uint32_t kScatWaves = kAggThreads / 64;
 
-// Capped cells (the count-free layout of a triage run):
+// The capped scatters' tuning (measured alternatives: DESIGN.md section 8).
+constexpr uint32_t kScat3K = 16;        // k_scat3: records per lane per tile
+constexpr uint32_t kScat3KEntry = 10;   // ... with per-record levels (Minimize: the prios take registers)
+constexpr uint32_t kScat3Fill = 85;     // % of its tiles' lanes an item must fill for k_scat3 to take it
+constexpr uint32_t kScatPer = 12;       // k_agg_scatter_blk: records per lane per tile
+constexpr uint32_t kScatPerEntry = 10;  // ... for Minimize (the prios take registers too)
+constexpr uint32_t kBlk = 16;           // records per 64-B block
+constexpr uint32_t kDummyLines = 2048;  // CapCells::dummy lines (of 64 B)
+typedef uint32_t scat_v4u __attribute__((ext_vector_type(4)));  // a flush lane: 16 B
+
+// Capped cells (the count-free layout of a run):
 // chunk c's cells are consecutive regions of cap[c] records (a multiple of 64)
 // from base[c], partition after partition; the scatter writes cnt[p][c] and
 // raises *ovf when a cell receives more than its capacity (the run is then
@@ -356,55 +346,132 @@ struct CapCells {
 	uint32_t* ovf;         // set to 1 by a cell overflow
 	uint64_t nchunks;
 	uint32_t* dummy;       // one 64-B line per block: the target of stores that are not made
-	// Two triage scatters over one run (round 6): with split set, k_scat3 takes
-	// the work items its one-call tiles would fill (scat3_takes: sizes[] =
-	// records, tiles[] = k_scat3 tiles per item) and k_agg_scatter_blk the
-	// rest, each skipping the other's items
+	// With split set, k_scat3 takes the work items its one-call tiles would
+	// fill (scat3_takes: sizes[] = records, tiles[] = k_scat3 tiles per item)
+	// and k_agg_scatter_blk the rest, each skipping the other's items
 	const uint64_t* sizes = nullptr;
 	const uint32_t* tiles = nullptr;
 	bool split = false;
 	uint32_t tile = 1024;  // records per k_scat3 tile the tiles[] were counted in (set with tiles)
 };
 
-#ifndef SYZ_SCAT3  // triage runs: 0 = k_agg_scatter_blk only, 1 = k_scat3 for the items it fills
-#define SYZ_SCAT3 1
-#endif
-#ifndef SYZ_SCAT3_K  // records per lane per tile
-#define SYZ_SCAT3_K 16
-#endif
-#ifndef SYZ_SCAT3_ENTRY  // Minimize's work items (one shard) through k_scat3 too, split as for triage
-#define SYZ_SCAT3_ENTRY 1
-#endif
-#ifndef SYZ_SCAT3_FILL  // % of its tiles' lanes an item must fill for k_scat3 to take it
-#define SYZ_SCAT3_FILL 85
-#endif
-#ifndef SYZ_SCAT3_V  // k_scat3's flush: dwords per lane (1, or 4: 16-B lanes)
-#define SYZ_SCAT3_V 4
-#endif
-#ifndef SYZ_SCAT_V  // the same for k_agg_scatter_blk
-#define SYZ_SCAT_V 4
-#endif
-typedef uint32_t scat_v4u __attribute__((ext_vector_type(4)));
-#ifndef SYZ_SCAT3_T  // threads per workgroup (1024: 4 waves per SIMD, 128 registers; 768: 3, 168; 512: 2, 256)
-#define SYZ_SCAT3_T 1024
-#endif
-
 // k_scat3's tiles of one work item (every call in ceil(len / tile) tiles), and
-// the split between the two triage scatters: k_scat3 takes an item whose tiles
-// would be at least SYZ_SCAT3_FILL % full, k_agg_scatter_blk the others.
-#ifndef SYZ_SCAT3_KE  // records per lane per tile with per-record levels (Minimize: the prios take registers)
-#define SYZ_SCAT3_KE 10
-#endif
-constexpr uint32_t kScat3Tile = SYZ_SCAT3_K * 64, kScat3TileEntry = SYZ_SCAT3_KE * 64;
+// the split between the two capped scatters: k_scat3 takes an item whose tiles
+// would be at least kScat3Fill % full, k_agg_scatter_blk the others.
+constexpr uint32_t kScat3Tile = kScat3K * 64, kScat3TileEntry = kScat3KEntry * 64;
 __host__ __device__ inline uint64_t scat3_tiles(uint32_t len, uint32_t tile)
 {
 	return (len + tile - 1) / tile;
 }
 __device__ inline bool scat3_takes(uint64_t recs, uint32_t tiles, uint32_t tile)
 {
-	return recs * 100 >= (uint64_t)tiles * tile * SYZ_SCAT3_FILL;
+	return recs * 100 >= (uint64_t)tiles * tile * kScat3Fill;
 }
 
+// Minimize's per-record levels (kEntry): a record's level comes from its own
+// prio byte (AggSrc::elem_prio, parallel to sigs) through the run's prio ->
+// level table in LDS (an LDS read waits on lgkmcnt, not vmcnt).  kOn = false:
+// no table.
+template <bool kOn>
+struct PrioLevels {
+	uint8_t lvl[kOn ? 256 : 1];
+	__device__ __forceinline__ void load(const LevelMap& lm, uint32_t nthreads)
+	{
+		if (kOn) {
+			for (uint32_t i = threadIdx.x; i < 256; i += nthreads)
+				lvl[i] = lm.lvl[i];
+		}
+	}
+	// the level bits of a record with prio byte pv; bad |= a kept record's prio has no level
+	__device__ __forceinline__ uint32_t level(uint32_t pv, bool kept, bool& bad) const
+	{
+		const uint32_t lv = lvl[kOn ? pv : 0];
+		bad |= kept && lv == 0xff;
+		return lv & 3;
+	}
+	// at the kernel's end: report a prio without a level to AggSrc::bad_level
+	static __device__ __forceinline__ void report(bool bad, const AggSrc& x)
+	{
+		if (kOn && x.bad_level && __ballot(bad) && lane_id() == 0)
+			atomicOr(x.bad_level, 1u);
+	}
+};
+
+// The calls of one work item in LDS, and a wave's walk over them in quotas of
+// kPer records per lane: wave w takes local calls w, w + kScatWaves, ...
+// (k_agg_scatter and k_agg_scatter_blk; k_scat3 walks its calls as scalars).
+struct CallTable {
+	uint64_t start[kScatChunkMax];
+	uint32_t len[kScatChunkMax];
+	uint16_t meta[kScatChunkMax];  // AggGeom::meta of the call (level 0 where the records have their own)
+	template <bool kEntry>
+	__device__ __forceinline__ void load(const uint64_t* __restrict__ call_start, const uint32_t* __restrict__ call_len,
+	                                     const uint8_t* __restrict__ call_prio, const LevelMap& lm, const AggGeom& g,
+	                                     uint64_t c0, uint64_t cbeg, uint32_t nc)
+	{
+		for (uint32_t i = threadIdx.x; i < nc; i += blockDim.x) {
+			const uint64_t c = c0 + cbeg + i;
+			start[i] = call_start[c];
+			len[i] = call_len[c];
+			meta[i] = (uint16_t)g.meta(kEntry ? 0 : lm.lvl[call_prio[c]], cbeg + i);
+		}
+	}
+	// A record slot's loc = (wave call number j << 24) | offset in the call
+	// (calls hold < 2^24 records, batch validation); the wave's j-th call is
+	// local call w + j * kScatWaves (j < 2^cbits / kScatWaves <= 32).
+	__device__ __forceinline__ uint32_t call_of(uint32_t w, uint32_t loc) const { return w + (loc >> 24) * kScatWaves; }
+	// Issue the loads of wave w's next quota from its position (local call wc,
+	// offset wo inside it; both advanced): ev[] = elements, loc[] as above,
+	// kEntry: pv[] = prio bytes.  Returns how many records the quota has; the
+	// slots past them hold a clamped, valid address.
+	template <bool kEntry, uint32_t kPer>
+	__device__ __forceinline__ uint32_t fetch(uint32_t w, uint32_t lane, uint32_t nc, uint32_t& wc, uint32_t& wo,
+	                                          const uint32_t* __restrict__ sigs, const AggSrc& x, uint32_t (&ev)[kPer],
+	                                          uint32_t (&loc)[kPer], uint32_t (&pv)[kEntry ? kPer : 1]) const
+	{
+		constexpr uint32_t kQuota = kPer * 64;
+		uint32_t q = 0;
+		while (q < kQuota && wc < nc) {
+			const uint32_t ln = len[wc], m = min(kQuota - q, ln - wo);
+			const uint32_t tag = ((wc - w) / kScatWaves) << 24;
+			if (q == 0) {
+#pragma unroll
+				for (uint32_t u = 0; u < kPer; u++)
+					loc[u] = tag | wo;  // clamped default: a valid address
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < kPer; u++) {
+				const uint32_t i = u * 64 + lane;
+				loc[u] = i >= q && i < q + m ? tag | (wo + i - q) : loc[u];
+			}
+			q += m;
+			wo += m;
+			if (wo == ln) {
+				wc += kScatWaves;
+				wo = 0;
+			}
+		}
+		if (q) {
+#pragma unroll
+			for (uint32_t u = 0; u < kPer; u++) {
+				const uint64_t a = start[call_of(w, loc[u])] + (loc[u] & 0xFFFFFFu);
+				ev[u] = __builtin_nontemporal_load(&sigs[a]);
+				if (kEntry)
+					pv[kEntry ? u : 0] = (uint8_t)__builtin_nontemporal_load(&x.elem_prio[a]);
+			}
+		}
+		return q;
+	}
+};
+
+// Records of each chunk -> their counted cells (fixed by the scan, so no
+// global atomics).  A tile of kAggTile records lives in registers (kPer per
+// lane), is counting-sorted by partition into LDS and written out as one run
+// per partition; the runs of one chunk's consecutive tiles continue each other.
+// The next tile's loads are issued before the write-out of the current one,
+// so HBM reads overlap the stores instead of following them.
+// kEntry (Minimize): per-record levels (PrioLevels), and only the records
+// whose element shard x.shard owns are kept.
 template <bool kEntry>
 __global__ __launch_bounds__(kAggThreads) void k_agg_scatter(const uint32_t* __restrict__ sigs,
                                                              const uint64_t* __restrict__ call_start,
@@ -414,21 +481,16 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_scatter(const uint32_t* __r
                                                              const uint32_t* __restrict__ offs,
                                                              const uint64_t* __restrict__ rec_base, uint32_t* recs)
 {
-	constexpr uint32_t kWaves = kAggThreads / 64, kQuota = kAggTile / kWaves, kPer = kQuota / 64;
+	constexpr uint32_t kQuota = kAggTile / kScatWaves, kPer = kQuota / 64;
 	static_assert(kQuota % 64 == 0, "tile quota per wave");
 	__shared__ uint32_t t_rec[kAggTile];   // sorted by partition: packed records
 	__shared__ uint16_t t_part[kAggTile];  // ... and their partitions
 	__shared__ uint64_t cur[kAggMaxParts];
 	__shared__ uint32_t hist[kAggMaxParts], pos[kAggMaxParts];
-	__shared__ uint64_t c_start[kScatChunkMax];  // the chunk's calls
-	__shared__ uint32_t c_len[kScatChunkMax];
-	__shared__ uint16_t c_meta[kScatChunkMax];
-	__shared__ uint8_t s_lvl[kEntry ? 256 : 1];
+	__shared__ CallTable calls;
+	__shared__ PrioLevels<kEntry> levels;
 	const uint32_t P = 1u << g.pbits, cb = g.cbits(), ib = g.ibits;
-	if (kEntry) {
-		for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
-			s_lvl[i] = lm.lvl[i];
-	}
+	levels.load(lm, blockDim.x);
 	const uint32_t w = threadIdx.x >> 6, lane = lane_id();
 	const uint64_t ncalls = c1 - c0, nitems = (ncalls + (1ull << ib) - 1) >> ib;
 	const uint32_t per_t = (P + blockDim.x - 1) / blockDim.x;
@@ -440,54 +502,12 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_scatter(const uint32_t* __r
 			cur[i] = rec_base[i] + offs[ch * P + i];
 			hist[i] = 0;
 		}
-		for (uint32_t i = threadIdx.x; i < nc; i += blockDim.x) {
-			const uint64_t c = c0 + cbeg + i;
-			c_start[i] = call_start[c];
-			c_len[i] = call_len[c];
-			c_meta[i] = (uint16_t)g.meta(kEntry ? 0 : lm.lvl[call_prio[c]], cbeg + i);
-		}
+		calls.load<kEntry>(call_start, call_len, call_prio, lm, g, c0, cbeg, nc);
 		__syncthreads();
-		// this wave's walk: local call wc (then +kWaves), offset wo inside it
-		uint32_t wc = w, wo = 0;
-		// Per record slot: loc = (wave call number j << 24) | offset in the call
-		// (calls hold < 2^24 records, batch validation); the wave's j-th call
-		// is local call w + j * kWaves (j < 2^cbits / kWaves <= 32).
-		uint32_t ev[kPer], loc[kPer];
-		int8_t pv[kEntry ? kPer : 1];
-		// issue the loads of this wave's next quota; returns how many records it has
-		auto fetch = [&]() -> uint32_t {
-			uint32_t q = 0;
-			while (q < kQuota && wc < nc) {
-				const uint32_t len = c_len[wc], m = min(kQuota - q, len - wo);
-				const uint32_t tag = ((wc - w) / kWaves) << 24;
-				if (q == 0) {
-#pragma unroll
-					for (uint32_t u = 0; u < kPer; u++)
-						loc[u] = tag | wo;  // clamped default: a valid address
-				}
-#pragma unroll
-				for (uint32_t u = 0; u < kPer; u++) {
-					const uint32_t i = u * 64 + lane;
-					loc[u] = i >= q && i < q + m ? tag | (wo + i - q) : loc[u];
-				}
-				q += m;
-				wo += m;
-				if (wo == len) {
-					wc += kWaves;
-					wo = 0;
-				}
-			}
-			if (q) {
-#pragma unroll
-				for (uint32_t u = 0; u < kPer; u++) {
-					const uint64_t a = c_start[w + (loc[u] >> 24) * kWaves] + (loc[u] & 0xFFFFFFu);
-					ev[u] = __builtin_nontemporal_load(&sigs[a]);
-					if (kEntry)
-						pv[kEntry ? u : 0] = __builtin_nontemporal_load(&x.elem_prio[a]);
-				}
-			}
-			return q;
-		};
+		uint32_t wc = w, wo = 0;  // this wave's walk
+		uint32_t ev[kPer], loc[kPer], pv[kEntry ? kPer : 1];
+		// (through a lambda: called directly at both sites the kernel takes 11 more VGPRs)
+		auto fetch = [&]() { return calls.fetch<kEntry>(w, lane, nc, wc, wo, sigs, x, ev, loc, pv); };
 		uint32_t n = fetch();
 		for (;;) {
 			// stage: partition and rank of every record of the tile (loc = ~0: not kept)
@@ -498,12 +518,9 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_scatter(const uint32_t* __r
 				if (keep) {
 					const uint32_t h = fmix32(ev[u]), p = g.part(h);
 					const uint32_t r = atomicAdd(&hist[p], 1u);
-					uint32_t meta = c_meta[w + (loc[u] >> 24) * kWaves];
-					if (kEntry) {
-						const uint32_t lv = s_lvl[(uint8_t)pv[kEntry ? u : 0]];
-						badlv |= lv == 0xff;
-						meta |= (lv & 3) << cb;
-					}
+					uint32_t meta = calls.meta[calls.call_of(w, loc[u])];
+					if (kEntry)
+						meta |= levels.level(pv[kEntry ? u : 0], true, badlv) << cb;
 					ev[u] = g.rec(h, meta);
 					loc[u] = p | (r << 16);
 				} else {
@@ -551,330 +568,268 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_scatter(const uint32_t* __r
 				break;
 		}
 	}
-	if (kEntry && x.bad_level && __ballot(badlv) && lane == 0)
-		atomicOr(x.bad_level, 1u);
+	PrioLevels<kEntry>::report(badlv, x);
 }
 
-// Capped cells written in whole 64-B blocks (the triage runs' scatter).
+// The write-combining blocks of a capped scatter's workgroup.
 // A store costs one memory request per 64-B segment it touches, whatever the
 // bytes: a ~9-record piece of a cell at an arbitrary offset touches ~1.6
 // segments, a whole aligned block one (scripts/mb_scatter.hip: 2.0-2.3 vs
-// 3.4-3.8 TB/s read+write).  So every partition has a write-combining buffer
-// of one block in LDS (2048 x 64 B): records go from registers straight into
-// their partition's buffer (one ds_add_rtn for a slot, one ds_write), and a
-// buffer that fills is written out whole, 16 lanes per block; a record that
-// finds its buffer full waits for the flush (next sub-round).  No tile sort,
-// no scan.  A cell's last partial block is written when its chunk ends.
-constexpr uint32_t kBlk = 16;            // records per written block (64 B)
-constexpr uint32_t kDummyLines = 2048;  // CapCells::dummy lines
-// records per lane per tile
-#ifndef SYZ_SCAT_PER
-#define SYZ_SCAT_PER 12
-#endif
-#ifndef SYZ_SCAT_PER_ENTRY  // (Minimize: the prios take registers too)
-#define SYZ_SCAT_PER_ENTRY 10
-#endif
-
-// Work items of 2^ibits calls own their cells (items = chunks for a triage
-// batch).  kEntry (Minimize): the level comes from each record's own prio
-// (x.elem_prio), and only the records whose element shard x.shard owns are kept.
-// kMaxP: the partitions the LDS is sized for; kWpe: waves per SIMD the
-// registers are sized for (4: one workgroup per CU, 8: two, each with half
-// the LDS: 1024 partitions of 64-B blocks).
-template <bool kEntry, uint32_t kB, uint32_t kMaxP = kAggMaxParts, uint32_t kWpe = 4, uint32_t kT = kAggThreads>
-__global__ __launch_bounds__(kT, kWpe) void k_agg_scatter_blk(const uint32_t* __restrict__ sigs,
-                                                                 const uint64_t* __restrict__ call_start,
-                                                                 const uint32_t* __restrict__ call_len,
-                                                                 const uint8_t* __restrict__ call_prio, LevelMap lm,
-                                                                 uint64_t c0, uint64_t c1, AggGeom g, AggSrc x,
-                                                                 CapCells cc, uint32_t* recs, uint32_t dbg)
-{
-	constexpr uint32_t kWaves = kT / 64, kPer = kEntry ? SYZ_SCAT_PER_ENTRY : SYZ_SCAT_PER, kQuota = kPer * 64;
-	constexpr uint32_t kG = 64 / kB;  // blocks a wave writes per store (kB lanes each)
+// 3.4-3.8 TB/s read+write).  So every partition has a buffer of one block of
+// kB records in LDS: 2048 partitions x 16 records (64 B), or 1024 partitions
+// x 32 records (128 B, a whole line) -- 128 KB either way.  A work item is
+// scattered in sub-rounds:
+//   place   every pending record claims a slot in its partition's block (one
+//           ds_add_rtn, all claims of a tile in flight together) and is
+//           written there (one ds_write), or, its block being full, stays
+//           pending for the next sub-round;
+//   wg_or   one barrier, which also tells whether any record is still pending;
+//   flush   no list of full blocks is built while placing: each wave scans
+//           the counts of its own share of the partitions (partition
+//           i * kAggThreads + w * 64 + lane) and writes the full blocks of
+//           its share to their cells, 16 B per lane (ds_read_b128,
+//           global_store_dwordx4).  A lane group without a block, or whose
+//           block no longer fits its cell, stores to the workgroup's dummy
+//           line instead (the same instruction count on every path).
+// No tile sort, no scan of the tile.  finish() writes each cell's last
+// partial block and the cell counts when the work item ends.
+struct ScatLane {  // one thread's registers for ScatBlocks
+	uint32_t w, lane;      // its wave in the workgroup (uniform) and lane
+	uint32_t seq = 0;      // wg_or's row in turn
+	bool spilled = false;  // a block or a tail did not fit its cell: the run is redone with counted cells
+};
+struct ScatItem {  // the cells of the work item being scattered
+	uint32_t* recs;
+	uint64_t base;  // CapCells::base and cap of the item
+	uint32_t cap;
+};
+template <uint32_t kB>
+struct ScatBlocks {
 	static_assert(kB == 16 || kB == 32, "block of 64 or 128 B");
-	constexpr uint32_t kChunkMax = kMaxP / 4;        // calls per chunk (cbits = pbits - 2)
-	__shared__ __align__(16) uint32_t buf[kMaxP * (kMaxP == kAggMaxParts ? kBlk : kB)];  // per partition: the block being filled
-	__shared__ uint32_t fillc[kMaxP + 1];   // slots handed out in it (may overshoot kB)
-	__shared__ uint32_t written[kMaxP + 1]; // records of the cell written so far (+ a spare)
-	// full blocks found after the sub-round's barrier by a scan of the counts,
-	// every wave over its own share of the partitions (as in k_scat3)
-	constexpr uint32_t kShare = (kMaxP + kT - 1) / kT;  // partitions per lane in the scan
-	__shared__ uint16_t flist[kShare * kT]; // per wave: partitions whose block filled this sub-round
-	__shared__ uint64_t c_start[kChunkMax]; // the chunk's calls
-	__shared__ uint32_t c_len[kChunkMax];
-	__shared__ uint16_t c_meta[kChunkMax];
-	__shared__ uint8_t s_lvl[kEntry ? 256 : 1];
-	__shared__ uint32_t s_or[2][kWaves];
-	const uint32_t P = 1u << g.pbits, cb = g.cbits(), ib = g.ibits;
-	// the flush: kV dwords per lane (16-B lanes as in k_scat3)
-	constexpr uint32_t kV = SYZ_SCAT_V, kLB = kB / kV, kGF = 64 / kLB;
-	using FV = std::conditional_t<kV == 4, scat_v4u, uint32_t>;
-	const uint32_t w = threadIdx.x >> 6, lane = lane_id(), grp = lane / kB, slot = lane & (kB - 1), fgrp = lane / kLB,
-	               fq = lane % kLB;
+	static constexpr uint32_t kMaxP = kB == 16 ? 2048 : 1024;  // partitions
+	static_assert(kMaxP * kB * 4 == 128 * 1024 && kMaxP <= kAggMaxParts, "128 KB of blocks");
+	static constexpr uint32_t kG = 64 / kB;                   // finish: cells per wave and pass (kB lanes each)
+	static constexpr uint32_t kLB = kB / 4, kGF = 64 / kLB;  // flush: 16-B lanes per block, blocks per wave store
+	static constexpr uint32_t kShare = (kMaxP + kAggThreads - 1) / kAggThreads;  // partitions per lane in the scan
+	alignas(16) uint32_t buf[kMaxP * kB];    // per partition: the block being filled
+	uint32_t fillc[kMaxP + 1];               // slots handed out in it (may overshoot kB)
+	uint32_t written[kMaxP + 1];             // records of the cell written so far (+ a spare)
+	uint16_t flist[kShare * kAggThreads];    // per wave: partitions of its share whose block filled this sub-round
+	uint32_t s_or[2][kScatWaves];
+
+	// a new work item (a barrier must follow)
+	__device__ __forceinline__ void reset(uint32_t P)
+	{
+		for (uint32_t i = threadIdx.x; i < P; i += kAggThreads) {
+			fillc[i] = 0;
+			written[i] = 0;
+		}
+	}
 	// Workgroup OR in one barrier (__syncthreads_or takes three): every wave
-	// writes its flag to a row, all read the row; two rows alternate, so a row
-	// is rewritten only after every wave passed the barrier of the call between.
-	uint32_t seq = 0;
-	auto wg_or = [&](bool pred) -> bool {
-		uint32_t* r = s_or[seq++ & 1];
+	// writes its flag to a row, all read the row (lane i reads wave i's flag);
+	// two rows alternate, so a row is rewritten only after every wave passed
+	// the barrier of the call between.
+	__device__ __forceinline__ bool wg_or(ScatLane& t, bool pred)
+	{
+		uint32_t* r = s_or[t.seq++ & 1];
 		const bool any = __ballot(pred) != 0;
-		if (lane == 0)
-			r[w] = any;
+		if (t.lane == 0)
+			r[t.w] = any;
 		__syncthreads();
-		return __ballot(r[lane & (kWaves - 1)] != 0) != 0;  // lane i reads wave i's flag
-	};
+		return __ballot(r[t.lane & (kScatWaves - 1)] != 0) != 0;
+	}
+	// one placement pass over a tile's records rec[] of partitions pt[]: pend
+	// = the mask of those to place; returns what is left
+	template <uint32_t M>
+	__device__ __forceinline__ uint32_t place(const uint32_t (&rec)[M], const uint32_t (&pt)[M], uint32_t pend)
+	{
+		uint32_t sl[M];
+#pragma unroll
+		for (uint32_t u = 0; u < M; u++)
+			sl[u] = (pend >> u) & 1 ? atomicAdd(&fillc[pt[u]], 1u) : kB;
+#pragma unroll
+		for (uint32_t u = 0; u < M; u++) {
+			if (sl[u] < kB) {
+				buf[pt[u] * kB + sl[u]] = rec[u];
+				pend &= ~(1u << u);
+			}
+		}
+		return pend;
+	}
+	// write out the blocks of this wave's share that filled in this sub-round
+	__device__ __forceinline__ void flush(ScatLane& t, uint32_t P, const ScatItem& it, uint32_t* dummy)
+	{
+		const uint32_t fgrp = t.lane / kLB, fq = t.lane % kLB;
+		uint16_t* wl = flist + t.w * kShare * 64;  // this wave's list
+		uint32_t nw = 0;
+#pragma unroll
+		for (uint32_t i = 0; i < kShare; i++) {
+			const uint32_t p = i * kAggThreads + t.w * 64 + t.lane;
+			const bool f = p < P && fillc[p] >= kB;
+			const uint64_t m = __ballot(f);
+			if (f)
+				wl[nw + lane_rank(m)] = (uint16_t)p;
+			nw += (uint32_t)__popcll(m);
+		}
+		// (the wave's LDS operations run in order: the list is read below as written)
+		for (uint32_t jb = 0; jb < nw; jb += kGF) {
+			const bool ok = jb + fgrp < nw;
+			const uint32_t pp = wl[min(jb + fgrp, nw - 1)];
+			const uint32_t wr = written[pp];
+			const scat_v4u v = *reinterpret_cast<const scat_v4u*>(&buf[pp * kB + fq * 4]);
+			const bool fits = wr + kB <= it.cap;
+			t.spilled |= ok && !fits;
+			uint32_t* d = ok && fits ? it.recs + it.base + (uint64_t)pp * it.cap + wr
+			                         : dummy + (blockIdx.x % (kDummyLines * kBlk / kB)) * kB;
+			*reinterpret_cast<scat_v4u*>(d + fq * 4) = v;
+			__builtin_amdgcn_wave_barrier();
+			if (fq == 0 && ok) {
+				written[pp] = wr + kB;
+				fillc[pp] = 0;
+			}
+		}
+	}
+	// one tile: place in sub-rounds until every record is in a block
+	template <uint32_t M>
+	__device__ __forceinline__ void scatter_tile(ScatLane& t, uint32_t P, const ScatItem& it, uint32_t* dummy,
+	                                             const uint32_t (&rec)[M], const uint32_t (&pt)[M], uint32_t pend)
+	{
+		for (;;) {
+			pend = place(rec, pt, pend);
+			const bool more = wg_or(t, pend != 0);
+			flush(t, P, it, dummy);
+			if (!more)
+				break;
+			__syncthreads();
+		}
+	}
+	// The end of work item ch: every cell's last partial block and its count,
+	// and the run's spill flag; ends with the barrier before the next reset.
+	// The flag is raised here, at the end of the item that spilled, not once at
+	// the kernel's end, on purpose: it keeps the flag's address out of what a
+	// later store after the item loop would hold live (measured: fewer SGPR
+	// spills).  The run is void either way; a workgroup
+	// of the same launch that starts late may see the flag and return at once.
+	__device__ __forceinline__ void finish(ScatLane& t, uint32_t P, const ScatItem& it, const CapCells& cc, uint64_t ch)
+	{
+		const uint32_t grp = t.lane / kB, slot = t.lane & (kB - 1);
+		for (uint32_t p = t.w * kG + grp; p < P; p += kScatWaves * kG) {
+			const uint32_t c = fillc[p], wr = written[p];
+			if (wr + c > it.cap)
+				t.spilled = true;
+			else if (slot < c)
+				it.recs[it.base + (uint64_t)p * it.cap + wr + slot] = buf[p * kB + slot];
+			if (slot == 0)
+				cc.cnt[(uint64_t)p * cc.nchunks + ch] = min(wr + c, it.cap);
+		}
+		if (t.spilled)
+			*cc.ovf = 1u;
+		__syncthreads();
+	}
+};
+
+// Capped cells, a wave's tile of kPer records per lane walks the item's calls
+// through the CallTable: it is full whatever the calls' lengths, at the price
+// of per-record call bookkeeping (loc, an LDS lookup of the call's start and
+// meta).  Takes the work items k_scat3 leaves (cc.split), or all of them.
+// kEntry (Minimize): per-record levels (PrioLevels), and only the records
+// whose element shard x.shard owns are kept.
+template <bool kEntry, uint32_t kB>
+__global__ __launch_bounds__(kAggThreads, 4) void k_agg_scatter_blk(const uint32_t* __restrict__ sigs,
+                                                                    const uint64_t* __restrict__ call_start,
+                                                                    const uint32_t* __restrict__ call_len,
+                                                                    const uint8_t* __restrict__ call_prio, LevelMap lm,
+                                                                    uint64_t c0, uint64_t c1, AggGeom g, AggSrc x,
+                                                                    CapCells cc, uint32_t* recs)
+{
+	constexpr uint32_t kPer = kEntry ? kScatPerEntry : kScatPer;
+	__shared__ ScatBlocks<kB> blocks;
+	__shared__ CallTable calls;
+	__shared__ PrioLevels<kEntry> levels;
+	const uint32_t P = 1u << g.pbits, cb = g.cbits(), ib = g.ibits;
+	ScatLane t{threadIdx.x >> 6, lane_id()};
+	const uint32_t w = t.w, lane = t.lane;
 	const uint64_t ncalls = c1 - c0, nchunks = (ncalls + (1ull << ib) - 1) >> ib;  // work items
 	if (*cc.ovf)
 		return;  // the run is already void (an optimistic run's assumptions failed, or a cell spilled)
-	bool spilled = false, badlv = false;
-	if (kEntry) {
-		for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
-			s_lvl[kEntry ? i : 0] = lm.lvl[i];
-	}
+	bool badlv = false;
+	levels.load(lm, blockDim.x);
 	for (uint64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
 		const uint64_t cbeg = ch << ib;
 		const uint32_t nc = (uint32_t)min<uint64_t>(ncalls - cbeg, 1ull << ib);
 		if (cc.split && scat3_takes(cc.sizes[ch], cc.tiles[ch], cc.tile))
 			continue;  // long calls: k_scat3's item
-		const uint32_t cap = cc.cap[ch];
-		const uint64_t cbase = cc.base[ch];
-		for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
-			fillc[i] = 0;
-			written[i] = 0;
-		}
-		for (uint32_t i = threadIdx.x; i < nc; i += blockDim.x) {
-			const uint64_t c = c0 + cbeg + i;
-			c_start[i] = call_start[c];
-			c_len[i] = call_len[c];
-			c_meta[i] = (uint16_t)g.meta(kEntry ? 0 : lm.lvl[call_prio[c]], cbeg + i);
-		}
+		const ScatItem it{recs, cc.base[ch], cc.cap[ch]};
+		blocks.reset(P);
+		calls.load<kEntry>(call_start, call_len, call_prio, lm, g, c0, cbeg, nc);
 		__syncthreads();
-		uint32_t wc = w, wo = 0;  // this wave's walk: local call wc (then +kWaves), offset wo inside it
-		uint32_t pv[kEntry ? kPer : 1];  // kEntry: the records' prios (of the last fetch)
-		// issue the loads of this wave's next quota; returns how many records it has
-		auto fetch = [&](uint32_t (&ev)[kPer], uint32_t (&loc)[kPer]) -> uint32_t {
-			uint32_t q = 0;
-			while (q < kQuota && wc < nc) {
-				const uint32_t len = c_len[wc], m = min(kQuota - q, len - wo);
-				const uint32_t tag = ((wc - w) / kWaves) << 24;
-				if (q == 0) {
-#pragma unroll
-					for (uint32_t u = 0; u < kPer; u++)
-						loc[u] = tag | wo;  // clamped default: a valid address
-				}
-#pragma unroll
-				for (uint32_t u = 0; u < kPer; u++) {
-					const uint32_t i = u * 64 + lane;
-					loc[u] = i >= q && i < q + m ? tag | (wo + i - q) : loc[u];
-				}
-				q += m;
-				wo += m;
-				if (wo == len) {
-					wc += kWaves;
-					wo = 0;
-				}
-			}
-			if (q) {
-#pragma unroll
-				for (uint32_t u = 0; u < kPer; u++) {
-					const uint64_t at = c_start[w + (loc[u] >> 24) * kWaves] + (loc[u] & 0xFFFFFFu);
-					ev[u] = __builtin_nontemporal_load(&sigs[at]);
-					if (kEntry)
-						pv[kEntry ? u : 0] = (uint8_t)__builtin_nontemporal_load(&x.elem_prio[at]);
-				}
-			}
-			return q;
-		};
-		// write out the blocks of this wave's share that filled in this
-		// sub-round: kLB lanes per block
-		auto flush = [&]() {
-			uint16_t* wl = flist + w * kShare * 64;  // this wave's list
-			uint32_t nw = 0;
-#pragma unroll
-			for (uint32_t i = 0; i < kShare; i++) {
-				const uint32_t p = i * kT + w * 64 + lane;
-				const bool f = p < P && fillc[p] >= kB;
-				const uint64_t m = __ballot(f);
-				if (f)
-					wl[nw + lane_rank(m)] = (uint16_t)p;
-				nw += (uint32_t)__popcll(m);
-			}
-			// (the wave's LDS operations run in order: the list is read below as written)
-			for (uint32_t jb = 0; jb < nw; jb += kGF) {
-				const bool ok = jb + fgrp < nw;
-				const uint32_t pp = wl[min(jb + fgrp, nw - 1)];
-				const uint32_t wr = written[pp];
-				const FV v = *reinterpret_cast<const FV*>(&buf[pp * kB + fq * kV]);
-				const bool fits = wr + kB <= cap;
-				spilled |= ok && !fits;  // the cell is full: the run is redone with counted cells
-				uint32_t* d = ok && fits ? recs + cbase + (uint64_t)pp * cap + wr
-				                         : cc.dummy + (blockIdx.x % (kDummyLines * kBlk / kB)) * kB;
-				*reinterpret_cast<FV*>(d + fq * kV) = v;
-				__builtin_amdgcn_wave_barrier();
-				if (fq == 0 && ok) {
-					written[pp] = wr + kB;
-					fillc[pp] = 0;
-				}
-			}
-		};
-		// a tile's records: packed record and partition, and the mask of those to place
-		auto pack = [&](const uint32_t (&ev)[kPer], const uint32_t (&loc)[kPer], uint32_t n, uint32_t (&rec)[kPer],
-		                uint32_t (&pt)[kPer]) -> uint32_t {
-			uint32_t pend = 0;
+		uint32_t wc = w, wo = 0;  // this wave's walk
+		uint32_t ev[kPer], loc[kPer], pv[kEntry ? kPer : 1];
+		uint32_t n = calls.fetch<kEntry>(w, lane, nc, wc, wo, sigs, x, ev, loc, pv);
+		for (;;) {
+			// the tile's packed records and partitions, and the mask of those to place
+			uint32_t rec[kPer], pt[kPer], pend = 0;
 #pragma unroll
 			for (uint32_t u = 0; u < kPer; u++) {
 				const uint32_t h = fmix32(ev[u]);
 				pt[u] = g.part(h);
-				uint32_t meta = c_meta[w + (loc[u] >> 24) * kWaves];
+				uint32_t meta = calls.meta[calls.call_of(w, loc[u])];
 				const bool keep = !kEntry || x.nshards == 1 || owner_of(ev[u], x.nshards) == x.shard;
-				if (kEntry) {
-					const uint32_t lv = s_lvl[pv[kEntry ? u : 0]];
-					badlv |= u * 64 + lane < n && keep && lv == 0xff;
-					meta |= (lv & 3) << cb;
-				}
+				if (kEntry)
+					meta |= levels.level(pv[kEntry ? u : 0], u * 64 + lane < n && keep, badlv) << cb;
 				rec[u] = g.rec(h, meta);
 				pend |= (uint32_t)(u * 64 + lane < n && keep) << u;
 			}
-#ifdef SYZ_EXPERIMENTS
-			return dbg & 2 ? 0u : pend;  // dbg & 2: timing only, records loaded and dropped
-#else
-			// (the bit is SYZSIG_DEBUG_EDGE_PASSES >> 10 in product builds: ignored here)
-			return pend;
-#endif
-		};
-		// one placement pass: a slot in each record's partition block (all slot
-		// requests in flight together), or it waits for the block's flush.
-		// Returns what is left.
-		auto place = [&](const uint32_t (&rec)[kPer], const uint32_t (&pt)[kPer], uint32_t pend) -> uint32_t {
-			uint32_t sl[kPer];
-#pragma unroll
-			for (uint32_t u = 0; u < kPer; u++)
-				sl[u] = (pend >> u) & 1 ? atomicAdd(&fillc[pt[u]], 1u) : kB;
-#pragma unroll
-			for (uint32_t u = 0; u < kPer; u++) {
-				if (sl[u] < kB) {
-					buf[pt[u] * kB + sl[u]] = rec[u];
-					pend &= ~(1u << u);
-				}
-			}
-			return pend;
-		};
-		uint32_t ev[kPer], loc[kPer];
-		uint32_t n = fetch(ev, loc);
-		for (;;) {
-			uint32_t rec[kPer], pt[kPer];
-			uint32_t pend = pack(ev, loc, n, rec, pt);
-			n = fetch(ev, loc);  // the next tile's loads fly while this one is placed
-			for (;;) {
-				pend = place(rec, pt, pend);
-				const bool more = wg_or(pend != 0);
-				flush();
-				if (!more)
-					break;
-				__syncthreads();
-			}
-			if (!wg_or(n != 0))  // (its barrier also ends the last flush)
+			n = calls.fetch<kEntry>(w, lane, nc, wc, wo, sigs, x, ev, loc, pv);  // the next tile's loads fly while this one is placed
+			blocks.scatter_tile(t, P, it, cc.dummy, rec, pt, pend);
+			if (!blocks.wg_or(t, n != 0))  // (its barrier also ends the last flush)
 				break;
 		}
-		// the chunk's last partial block of every cell, and the cell counts
-		for (uint32_t p = w * kG + grp; p < P; p += kWaves * kG) {
-			const uint32_t c = fillc[p], wr = written[p];
-			if (wr + c > cap)
-				spilled = true;
-			else if (slot < c)
-				recs[cbase + (uint64_t)p * cap + wr + slot] = buf[p * kB + slot];
-			if (slot == 0)
-				cc.cnt[(uint64_t)p * cc.nchunks + ch] = min(wr + c, cap);
-		}
-		__syncthreads();  // fillc/written/buf are reset by the next chunk
+		blocks.finish(t, P, it, cc, ch);
 	}
-	if (spilled)
-		*cc.ovf = 1u;
-	if (kEntry && x.bad_level && __ballot(badlv) && lane == 0)
-		atomicOr(x.bad_level, 1u);
+	PrioLevels<kEntry>::report(badlv, x);
 }
 
-// The lean scatter of triage runs (round 6): the same capped cells and 64-B
-// write-combining blocks, with the per-record bookkeeping of the loads taken
-// out.  A wave walks whole calls (calls w, w + kWaves, .. of its chunk) in
-// tiles of up to kK * 64 records of ONE call: the tile's start, level and
-// serial are wave-uniform scalars (s_load of the call, no LDS call table),
-// so a record costs its load, fmix32, one ds_add_rtn and one ds_write.
-// The kernel was bound by VALU issue (about 1,200 vector instructions per
-// wave and tile of 16 records per lane), so: the flush moves 16 B per lane
-// (ds_read_b128, global_store_dwordx4: a quarter of its instructions of 4-B
-// lanes), the pending mask comes from the record count, and no flush list is
-// built while placing (no per-record "block full" test, no list append):
-// after the sub-round's barrier each wave scans the counts of its own share
-// of the partitions and flushes the blocks of its share that filled.
-// Variants measured slower and removed: two
-// workgroups per CU each placing one half of the partitions, records that
-// met a full block carried in registers to the next tile, and one slot claim
-// per record with the claims past a full block written into its next fill
-// (half the barriers, no second claim, but more instructions per tile).
-template <uint32_t kT, uint32_t kK, uint32_t kWpe, bool kEntry = false, uint32_t kB = kBlk>
-__global__ __launch_bounds__(kT, kWpe) void k_scat3(const uint32_t* __restrict__ sigs,
-                                                    const uint64_t* __restrict__ call_start,
-                                                    const uint32_t* __restrict__ call_len,
-                                                    const uint8_t* __restrict__ call_prio, LevelMap lm, uint64_t c0,
-                                                    uint64_t c1, AggGeom g, CapCells cc, uint32_t* recs, AggSrc x)
+// Capped cells, the lean scatter: the per-record bookkeeping of the loads is
+// taken out.  A wave walks whole calls (calls w, w + kScatWaves, .. of its
+// work item) in tiles of up to kK * 64 records of ONE call: the tile's start,
+// level and serial are wave-uniform scalars (s_load of the call, no LDS call
+// table), and the pending mask comes from the record count, so a record costs
+// its load, fmix32, one ds_add_rtn and one ds_write.  A call a little longer
+// than a tile leaves lanes idle: with cc.split the kernel takes only the work
+// items whose tiles it would fill (scat3_takes).
+// kEntry (Minimize, one shard): per-record levels (PrioLevels).
+template <uint32_t kK, bool kEntry, uint32_t kB>
+__global__ __launch_bounds__(kAggThreads, 4) void k_scat3(const uint32_t* __restrict__ sigs,
+                                                          const uint64_t* __restrict__ call_start,
+                                                          const uint32_t* __restrict__ call_len,
+                                                          const uint8_t* __restrict__ call_prio, LevelMap lm,
+                                                          uint64_t c0, uint64_t c1, AggGeom g, CapCells cc,
+                                                          uint32_t* recs, AggSrc x)
 {
-	// kEntry (Minimize, one shard): every record's level comes from its own
-	// prio (x.elem_prio, parallel to sigs); kB = 32: 128-B blocks for <= 1024
-	// partitions (the same 128 KB of LDS)
-	constexpr uint32_t kWaves = kT / 64, kG = 64 / kB, kTile = kK * 64;
-	constexpr uint32_t kMaxP = kAggMaxParts * kBlk / kB;
-	static_assert(kB == 16 || kB == 32, "block of 64 or 128 B");
-	// a flush lane moves kV dwords (4: 16-B LDS reads and block stores, kB / 4
-	// lanes per block -- a quarter of the flush's instructions of 4-B lanes)
-	constexpr uint32_t kV = SYZ_SCAT3_V, kLB = kB / kV, kGF = 64 / kLB;
-	using FV = std::conditional_t<kV == 4, scat_v4u, uint32_t>;
-	static_assert(kV == 1 || kV == 4, "flush lanes of 4 or 16 B");
+	constexpr uint32_t kTile = kK * 64;
 	static_assert(kK <= 31, "pending masks are 32-bit");
-	__shared__ __align__(16) uint32_t buf[kMaxP * kB];  // per partition: the block being filled
-	__shared__ uint32_t fillc[kMaxP + 1];     // slots handed out in it (may overshoot kB)
-	__shared__ uint32_t written[kMaxP + 1];   // records of the cell written so far (+ a spare)
-	// No flush list is built while placing: after the sub-round's barrier
-	// every wave scans its own share of the partitions' counts (partition
-	// i * kT + w * 64 + lane) and flushes the blocks of its share that filled,
-	// listed in its own slice of flist
-	constexpr uint32_t kShare = (kMaxP + kT - 1) / kT;  // partitions per lane in the scan
-	__shared__ uint16_t flist[kShare * kT];   // per wave: partitions whose block filled this sub-round
-	__shared__ uint32_t s_or[2][kWaves];
-	__shared__ uint8_t s_lvl[256];            // prio -> level (an LDS read: lgkmcnt, not vmcnt)
-	const uint32_t Pl = 1u << g.pbits;
+	__shared__ ScatBlocks<kB> blocks;
+	__shared__ PrioLevels<true> levels;  // (also the calls' levels: an LDS read)
+	const uint32_t P = 1u << g.pbits;
 	// (w through readfirstlane: the compiler then knows the call walk is
 	// wave-uniform and reads the calls with scalar loads, which wait on
 	// lgkmcnt -- a vector load there would need vmcnt(0), draining the
 	// prefetch and the block stores)
-	const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id(), grp = lane / kB,
-	               slot = lane & (kB - 1), fgrp = lane / kLB, fq = lane % kLB;
-	uint32_t seq = 0;
-	auto wg_or = [&](bool pred) -> bool {  // workgroup OR in one barrier (k_agg_scatter_blk)
-		uint32_t* r = s_or[seq++ & 1];
-		const bool any = __ballot(pred) != 0;
-		if (lane == 0)
-			r[w] = any;
-		__syncthreads();
-		return __ballot(lane < kWaves && r[lane < kWaves ? lane : 0] != 0) != 0;
-	};
+	ScatLane t{(uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane_id()};
+	const uint32_t w = t.w, lane = t.lane;
 	const uint64_t ncalls = c1 - c0, nchunks = (ncalls + (1ull << g.ibits) - 1) >> g.ibits;
 	if (*cc.ovf)
 		return;  // the run is already void
-	bool spilled = false, badlv = false;
-	for (uint32_t i = threadIdx.x; i < 256; i += kT)
-		s_lvl[i] = lm.lvl[i];
+	bool badlv = false;
+	levels.load(lm, kAggThreads);
 	for (uint64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {  // work items
 		const uint64_t cbeg = ch << g.ibits;
 		const uint32_t nc = (uint32_t)min<uint64_t>(ncalls - cbeg, 1ull << g.ibits);
 		if (cc.split && !scat3_takes(cc.sizes[ch], cc.tiles[ch], cc.tile))
 			continue;  // short calls: k_agg_scatter_blk's item
-		const uint32_t cap = cc.cap[ch];
-		const uint64_t cbase = cc.base[ch];
-		for (uint32_t i = threadIdx.x; i < Pl; i += kT) {
-			fillc[i] = 0;
-			written[i] = 0;
-		}
+		const ScatItem it{recs, cc.base[ch], cc.cap[ch]};
+		blocks.reset(P);
 		__syncthreads();
 		// this wave's call walk (wave-uniform): call j of the chunk, offset wo
 		uint32_t j = w, wo = 0, clen = 0, cmeta = 0;
@@ -890,10 +845,10 @@ __global__ __launch_bounds__(kT, kWpe) void k_scat3(const uint32_t* __restrict__
 					const uintptr_t pa = (uintptr_t)(call_prio + c);
 					const uint32_t word =
 					    *(const __attribute__((address_space(4))) uint32_t*)(pa & ~(uintptr_t)3);  // (constant: s_load)
-					cmeta = g.meta(kEntry ? 0 : s_lvl[(word >> (8 * (pa & 3))) & 0xFF], cbeg + j);
+					cmeta = g.meta(kEntry ? 0 : levels.lvl[(word >> (8 * (pa & 3))) & 0xFF], cbeg + j);
 					return;
 				}
-				j += kWaves;
+				j += kScatWaves;
 			}
 		};
 		open_call();
@@ -916,93 +871,26 @@ __global__ __launch_bounds__(kT, kWpe) void k_scat3(const uint32_t* __restrict__
 				wo += n;
 				if (wo == clen) {
 					wo = 0;
-					j += kWaves;
+					j += kScatWaves;
 					open_call();
 				}
 			}
 		};
-		auto flush = [&]() {
-			uint16_t* wl = flist + w * kShare * 64;  // this wave's list
-			uint32_t nw = 0;
-#pragma unroll
-			for (uint32_t i = 0; i < kShare; i++) {
-				const uint32_t p = i * kT + w * 64 + lane;
-				const bool f = p < Pl && fillc[p] >= kB;
-				const uint64_t m = __ballot(f);
-				if (f)
-					wl[nw + lane_rank(m)] = (uint16_t)p;
-				nw += (uint32_t)__popcll(m);
-			}
-			// (the wave's LDS operations run in order: the list is read below as written)
-			for (uint32_t jb = 0; jb < nw; jb += kGF) {
-				const bool ok = jb + fgrp < nw;
-				const uint32_t pp = wl[min(jb + fgrp, nw - 1)];
-				const uint32_t wr = written[pp];
-				const FV vv = *reinterpret_cast<const FV*>(&buf[pp * kB + fq * kV]);
-				const bool fits = wr + kB <= cap;
-				spilled |= ok && !fits;
-				uint32_t* d = ok && fits ? recs + cbase + (uint64_t)pp * cap + wr
-				                         : cc.dummy + (blockIdx.x % (kDummyLines * kBlk / kB)) * kB;
-				*reinterpret_cast<FV*>(d + fq * kV) = vv;
-				__builtin_amdgcn_wave_barrier();
-				if (fq == 0 && ok) {
-					written[pp] = wr + kB;
-					fillc[pp] = 0;
-				}
-			}
-		};
-		auto pack = [&](const uint32_t (&v)[kK], const uint32_t (&pv)[kEntry ? kK : 1], uint32_t n, uint32_t meta,
-		                uint32_t (&rec)[kK], uint32_t (&pt)[kK]) -> uint32_t {
-			uint32_t pend = 0;
-#pragma unroll
-			for (uint32_t u = 0; u < kK; u++) {
-				const uint32_t h = fmix32(v[u]), p = g.part(h);
-				pt[u] = p;
-				uint32_t m = meta;
-				if constexpr (kEntry) {
-					const uint32_t lv = s_lvl[pv[kEntry ? u : 0]];
-					badlv |= u * 64 + lane < n && lv == 0xff;
-					m |= (lv & 3) << g.cbits();
-				}
-				rec[u] = g.rec(h, m);
-			}
-			{  // records u * 64 + lane < n: the lane's first nu (a mask, not a compare per record)
-				const uint32_t nu = n > lane ? (n - lane + 63) >> 6 : 0u;  // (<= kK <= 31)
-				pend = (1u << nu) - 1;
-			}
-#if defined(SYZ_EXPERIMENTS) && defined(SYZ_SCAT3_DBG)  // timing only (results wrong): 1 = nothing placed
-			if (SYZ_SCAT3_DBG == 1)
-				pend = 0;
-#endif
-			return pend;
-		};
-		auto place = [&](const auto& rec, const auto& pt, uint32_t pend) -> uint32_t {
-			constexpr uint32_t M = sizeof(rec) / sizeof(rec[0]);
-			uint32_t sl[M];
-#pragma unroll
-			for (uint32_t u = 0; u < M; u++)
-				sl[u] = (pend >> u) & 1 ? atomicAdd(&fillc[pt[u]], 1u) : kB;
-#pragma unroll
-			for (uint32_t u = 0; u < M; u++) {
-				if (sl[u] < kB) {
-					buf[pt[u] * kB + sl[u]] = rec[u];
-					pend &= ~(1u << u);
-				}
-			}
-			return pend;
-		};
-		// one tile: place in sub-rounds until every record is in a block
+		// one tile: pack its records, then place them
 		auto tile = [&](const uint32_t (&v)[kK], const uint32_t (&pv)[kEntry ? kK : 1], uint32_t n, uint32_t meta) {
 			uint32_t rec[kK], pt[kK];
-			uint32_t pend = pack(v, pv, n, meta, rec, pt);
-			for (;;) {
-				pend = place(rec, pt, pend);
-				const bool more = wg_or(pend != 0);
-				flush();
-				if (!more)
-					break;
-				__syncthreads();
+#pragma unroll
+			for (uint32_t u = 0; u < kK; u++) {
+				const uint32_t h = fmix32(v[u]);
+				pt[u] = g.part(h);
+				uint32_t m = meta;
+				if constexpr (kEntry)
+					m |= levels.level(pv[kEntry ? u : 0], u * 64 + lane < n, badlv) << g.cbits();
+				rec[u] = g.rec(h, m);
 			}
+			// records u * 64 + lane < n: the lane's first nu (a mask, not a compare per record)
+			const uint32_t nu = n > lane ? (n - lane + 63) >> 6 : 0u;  // (<= kK <= 31)
+			blocks.scatter_tile(t, P, it, cc.dummy, rec, pt, (1u << nu) - 1);
 		};
 		// two register buffers in turn (static indices: the prefetch lands
 		// where it is consumed, no moves that would wait for it)
@@ -1011,78 +899,58 @@ __global__ __launch_bounds__(kT, kWpe) void k_scat3(const uint32_t* __restrict__
 		for (;;) {
 			fetch(vb, pb, nb, mb);
 			tile(va, pa, na, ma);
-			if (!wg_or(nb != 0))  // (its barrier also ends the last flush)
+			if (!blocks.wg_or(t, nb != 0))  // (its barrier also ends the last flush)
 				break;
 			fetch(va, pa, na, ma);
 			tile(vb, pb, nb, mb);
-			if (!wg_or(na != 0))
+			if (!blocks.wg_or(t, na != 0))
 				break;
 		}
-		// the chunk's last partial block of every cell, and the cell counts
-		for (uint32_t p = w * kG + grp; p < Pl; p += kWaves * kG) {
-			const uint32_t c = fillc[p], wr = written[p];
-			const uint32_t pg = p;
-			if (wr + c > cap)
-				spilled = true;
-			else if (slot < c)
-				recs[cbase + (uint64_t)pg * cap + wr + slot] = buf[p * kB + slot];
-			if (slot == 0)
-				cc.cnt[(uint64_t)pg * cc.nchunks + ch] = min(wr + c, cap);
-		}
-		__syncthreads();  // fillc/written/buf are reset by the next work item
+		blocks.finish(t, P, it, cc, ch);
 	}
-	if (spilled)
-		*cc.ovf = 1u;
-	if (kEntry && x.bad_level && __ballot(badlv) && lane == 0)
-		atomicOr(x.bad_level, 1u);
+	PrioLevels<kEntry>::report(badlv, x);
 }
 
-
-// The scatter's write-combining blocks fill the same 128 KB of LDS: 64 B per
-// partition at 2048 partitions, whole 128-B lines at <= 1024.
-#ifndef SYZ_SCAT_WIDE
-#define SYZ_SCAT_WIDE 1
-#endif
-// The triage runs' scatter (kEntry = false): k_scat3 when built with
-// SYZ_SCAT3 (at most kAggMaxParts partitions), else k_agg_scatter_blk.
-static void scatter_triage(uint64_t nchunks, hipStream_t s, uint32_t pbits, const uint32_t* sigs,
-                           const uint64_t* call_start, const uint32_t* call_len, const uint8_t* call_prio, LevelMap lm,
-                           uint64_t c0, uint64_t c1, AggGeom g, AggSrc x, CapCells cc, uint32_t* recs, uint32_t dbg);
 static uint64_t nchunks_of(uint64_t ncalls, uint32_t ibits)
 {
 	return (ncalls + (1ull << ibits) - 1) >> ibits;
 }
 
-template <bool kEntry, typename... A>
-static void scatter_blk(uint32_t grid, hipStream_t s, uint32_t pbits, A... a)
+// The capped-cell scatter of one run: which kernels, and the block width.
+// xp: Minimize's per-record extras (nullptr: a triage run).
+//   k_scat3 plus split: a triage run, or a Minimize run of one shard (its
+//       contexts come in rank order, Len desc, so the heavy first work items
+//       fill k_scat3's one-call tiles).  k_scat3's tiles hold one call's
+//       records, so the items whose tiles would be less than kScat3Fill % full
+//       go to k_agg_scatter_blk, decided per item on the device: both kernels
+//       are launched, each skips the other's items.
+//   k_agg_scatter_blk alone: a sharded Minimize part (the owner filter).
+// Blocks are 128 B at <= 1024 partitions (the same 128 KB of LDS), else 64 B;
+// a triage run's k_scat3 keeps 64-B blocks.
+static void launch_capped_scatter(hipStream_t s, const syzsig_batch* b, uint64_t c0, uint64_t c1, const LevelMap& lm,
+                                  const AggGeom& g, CapCells cc, uint32_t* recs, const AggSrc* xp)
 {
-	if (SYZ_SCAT_WIDE && pbits < kAggMaxBits)
-		k_agg_scatter_blk<kEntry, 32><<<grid, kAggThreads, 0, s>>>(a...);
-	else
-		k_agg_scatter_blk<kEntry, 16><<<grid, kAggThreads, 0, s>>>(a...);
-}
-
-static void scatter_triage(uint64_t nchunks, hipStream_t s, uint32_t pbits, const uint32_t* sigs,
-                           const uint64_t* call_start, const uint32_t* call_len, const uint8_t* call_prio, LevelMap lm,
-                           uint64_t c0, uint64_t c1, AggGeom g, AggSrc x, CapCells cc, uint32_t* recs, uint32_t dbg)
-{
-	if (SYZ_SCAT3 == 1) {
-		// k_scat3's tiles hold one call's records: calls a little longer than a
-		// tile leave lanes idle there, so items whose tiles would be less than
-		// SYZ_SCAT3_FILL % full go to k_agg_scatter_blk, decided per item on the
-		// device (both kernels are launched; each skips the other's items)
-		CapCells c2 = cc;
-		c2.split = cc.sizes && cc.tiles;
-		constexpr uint32_t kT = SYZ_SCAT3_T, kWpe = kT / 256;  // one workgroup per CU
-		k_scat3<kT, SYZ_SCAT3_K, kWpe><<<(uint32_t)std::min<uint64_t>(nchunks, 2048), kT, 0, s>>>(
-		    sigs, call_start, call_len, call_prio, lm, c0, c1, g, c2, recs, x);
-		if (c2.split)
-			scatter_blk<false>((uint32_t)std::min<uint64_t>(nchunks, 2048), s, pbits, sigs, call_start, call_len,
-			                   call_prio, lm, c0, c1, g, x, c2, recs, dbg);
-	} else {
-		scatter_blk<false>((uint32_t)std::min<uint64_t>(nchunks, 2048), s, pbits, sigs, call_start, call_len,
-		                   call_prio, lm, c0, c1, g, x, cc, recs, dbg);
+	const uint32_t grid = (uint32_t)std::min<uint64_t>(cc.nchunks, 2048);
+	const bool wide = g.pbits < kAggMaxBits;
+	const AggSrc x = xp ? *xp : AggSrc{nullptr, 1, 0, 0};
+	auto launch = [&](auto kernel, auto... tail) {
+		kernel<<<grid, kAggThreads, 0, s>>>(b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, tail...);
+	};
+	if (!xp || xp->nshards == 1) {
+		cc.split = xp || (cc.sizes && cc.tiles);
+		if (!xp)
+			launch(k_scat3<kScat3K, false, 16>, cc, recs, x);
+		else if (wide)
+			launch(k_scat3<kScat3KEntry, true, 32>, cc, recs, x);
+		else
+			launch(k_scat3<kScat3KEntry, true, 16>, cc, recs, x);
+		if (!cc.split)
+			return;
 	}
+	if (xp)
+		launch(wide ? k_agg_scatter_blk<true, 32> : k_agg_scatter_blk<true, 16>, x, cc, recs);
+	else
+		launch(wide ? k_agg_scatter_blk<false, 32> : k_agg_scatter_blk<false, 16>, x, cc, recs);
 }
 
 // Capped cells of a run: records per chunk -> cell capacity and chunk base.
@@ -1304,7 +1172,7 @@ __device__ __forceinline__ bool agg_partition(AggLds& L, uint32_t p, const AggCe
 	// resolve the queue: find-or-insert each element, then its level first
 	auto flush_queue = [&]() {
 		uint32_t ins = 0;
-		if (!SYZ_AGG_OVF_EACH && lds_flag(&L.s_ovf)) {  // overflowed: the partition is redone, skip the probes
+		if (lds_flag(&L.s_ovf)) {  // overflowed: the partition is redone, skip the probes
 			qn = 0;
 			return;
 		}
@@ -1462,7 +1330,7 @@ __device__ __forceinline__ bool agg_partition(AggLds& L, uint32_t p, const AggCe
 				lv[u] = g.level(r);
 				hb[u] = __umulhi(r & ~((1u << g.pbits) - 1), kAggBuckets);
 			}
-			// home buckets of all U records in flight together (ds_read_b128 / b64 each)
+			// home buckets of all U records in flight together (one ds_read_b128 each)
 			KBucket B[U];
 #pragma unroll
 			for (uint32_t u = 0; u < U; u++)
@@ -1513,9 +1381,9 @@ __device__ __forceinline__ bool agg_partition(AggLds& L, uint32_t p, const AggCe
 					o0 += U * 64;
 					// (the overflow flag is an LDS read, and its wait would also wait
 					// for this batch's ds_min: checked once per group of cells
-					// unless SYZ_AGG_OVF_EACH -- a full table ends every probe
-					// chain at once anyway, agg_find_insert)
-					more = o0 < n && (!SYZ_AGG_OVF_EACH || !lds_flag(&L.s_ovf));
+					// -- a full table ends every probe chain at once anyway,
+					// agg_find_insert)
+					more = o0 < n;
 				}
 			}
 		}
@@ -1695,8 +1563,7 @@ __global__ __launch_bounds__(kFinThreads) void k_agg_finalize(const uint32_t* __
                                                               LevelMap lm, uint64_t c0, uint64_t* slots,
                                                               uint64_t bmask, uint64_t* ns_slots, uint64_t ns_bmask,
                                                               uint8_t* call_new, uint64_t* pairs,
-                                                              unsigned long long* npairs, unsigned long long* ctr,
-                                                              uint32_t dbg)
+                                                              unsigned long long* npairs, unsigned long long* ctr)
 {
 	__shared__ uint64_t buf[kFinBuf];
 	__shared__ uint32_t s_n;
@@ -1775,7 +1642,7 @@ __global__ __launch_bounds__(kFinThreads) void k_agg_finalize(const uint32_t* __
 					slots[idx] = word;  // one entry per element: no other writer
 				inserted += !present;   // fresh, or an "absent" marker going live
 				changed++;
-				const int rr = (dbg & 8) ? 0 : tbl_merge_from(ns_slots, ns_bmask, e[k], P, bn[k]);  // dbg: timing only
+				const int rr = tbl_merge_from(ns_slots, ns_bmask, e[k], P, bn[k]);
 				ns_ins += rr == 1;
 				ovf += rr < 0;
 				// the staircase: first records of strictly rising level above M0[e]
@@ -1827,10 +1694,7 @@ __global__ __launch_bounds__(kFinThreads) void k_agg_finalize(const uint32_t* __
 // launch start sits before the first slot that was empty then; a slot seen
 // occupied, or claimed by another element, is occupied at launch end, so the
 // occupied-prefix invariant of every probe sequence still holds.
-#ifndef SYZ_FX_BUF
-#define SYZ_FX_BUF 2048
-#endif
-constexpr uint32_t kFxThreads = 512, kFxSet = 8192, kFxBuf = SYZ_FX_BUF, kFxProbe = 64;
+constexpr uint32_t kFxThreads = 512, kFxSet = 8192, kFxBuf = 2048, kFxProbe = 64;
 enum : int { kFxTaken = 0, kFxClaimed = 1, kFxFull = 2 };
 
 __device__ __forceinline__ int fx_claim(uint32_t* set, uint32_t tag, uint64_t rel)
@@ -1963,10 +1827,10 @@ __global__ __launch_bounds__(kFxThreads) void k_agg_finalize_x(
 				const int8_t P = lm.val[top[k]];
 				const uint64_t word = make_slot(e[k], P);
 				uint64_t old = 0;
-				// (dbg & 32, tests: defer every walk that leaves the home bucket)
+				// (SYZSIG_DEBUG_FIN_DEFER, tests: defer every walk that leaves the home bucket)
 				const uint64_t hm = home_bucket(e[k], bmask), hn = home_bucket(e[k], ns_bmask);
-				const int64_t idx = fx_walk(slots, hm, dbg & 32 ? hm + 1 : ms1, ms0 << kBucketShift, e[k], bm[k],
-				                            claim, 0, old);
+				const int64_t idx = fx_walk(slots, hm, dbg & SYZSIG_DEBUG_FIN_DEFER ? hm + 1 : ms1,
+				                            ms0 << kBucketShift, e[k], bm[k], claim, 0, old);
 				if (idx < 0) {  // the atomic path takes the whole element
 					const uint64_t d = atomicAdd(def_cnt, 1ull);
 					def_e[d] = e[k];
@@ -1981,8 +1845,8 @@ __global__ __launch_bounds__(kFxThreads) void k_agg_finalize_x(
 				inserted += !present; // fresh, or an "absent" marker going live
 				changed++;
 				uint64_t nold = 0;
-				const int64_t nidx = fx_walk(ns_slots, hn, dbg & 32 ? hn + 1 : ns1, ns0 << kBucketShift, e[k], bn[k],
-				                             claim, 1, nold);
+				const int64_t nidx = fx_walk(ns_slots, hn, dbg & SYZSIG_DEBUG_FIN_DEFER ? hn + 1 : ns1,
+				                             ns0 << kBucketShift, e[k], bn[k], claim, 1, nold);
 				if (nidx < 0) {
 					def_ns[atomicAdd(def_ns_cnt, 1ull)] = ((uint64_t)e[k] << 32) | prio_biased(P);
 				} else if (nold == 0 || nold < word) {
@@ -2436,26 +2300,7 @@ static int cap_scatter_agg(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, 
 {
 	const hipStream_t s = ctx->stream;
 	const CapCells cc{r.cbase, r.ccap, r.ccnt, r.ovf, r.nchunks, r.recs + r.bound, r.sizes, r.tiles, false, tile};
-	const int pg = (int)std::min<uint64_t>(r.nchunks, 2048);
-	if (xp && SYZ_SCAT3_ENTRY && xp->nshards == 1) {
-		// Minimize: the contexts in rank order (Len desc), so the heavy first
-		// work items fill k_scat3's one-call tiles; the split as for triage
-		CapCells c2 = cc;
-		c2.split = true;
-		if (g.pbits < kAggMaxBits)
-			k_scat3<kAggThreads, SYZ_SCAT3_KE, 4, true, 32><<<pg, kAggThreads, 0, s>>>(
-			    b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, c2, r.recs, *xp);
-		else
-			k_scat3<kAggThreads, SYZ_SCAT3_KE, 4, true, 16><<<pg, kAggThreads, 0, s>>>(
-			    b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, c2, r.recs, *xp);
-		scatter_blk<true>(pg, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, *xp, c2,
-		                  r.recs, ctx->agg_dbg >> 10);
-	} else if (xp)
-		scatter_blk<true>(pg, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g, *xp, cc,
-		                  r.recs, ctx->agg_dbg >> 10);
-	else
-		scatter_triage(r.nchunks, s, g.pbits, b->sigs, b->call_start, b->call_len, b->call_prio, lm, c0, c1, g,
-		               AggSrc{nullptr, 1, 0, 0}, cc, r.recs, ctx->agg_dbg >> 10);
+	launch_capped_scatter(s, b, c0, c1, lm, g, cc, r.recs, xp);
 	SYZ_HIP(hipGetLastError());
 	if (ev && ctx->timing)
 		SYZ_HIP(hipEventRecord(ev[1], s));
@@ -2581,7 +2426,7 @@ int agg_aggregate(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t 
 	// order) make the first chunks far heavier than the last: >= ~2048 items.
 	g.ibits = g.cbits();
 	if (entry)
-		while (g.ibits > 0 && ((c1 - c0) >> g.ibits) < SYZ_MIN_ITEMS)
+		while (g.ibits > 0 && ((c1 - c0) >> g.ibits) < kMinItems)
 			g.ibits--;
 	const bool counted_once = ctx->agg_counted_once;
 	ctx->agg_counted_once = false;
@@ -2988,7 +2833,7 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 			k_agg_finalize<<<(uint32_t)rc.size(), kFinThreads, 0, s>>>(
 			    (const uint32_t*)de2, (const uint4*)df2, (const uint32_t*)dc2, (uint32_t)rc.size(), lm, c0, ms->slots,
 			    ms->nbuckets - 1, nsp->slots, nsp->nbuckets - 1, b->call_new, (uint64_t*)pr, &ctx->d_cnt[kCntAux2],
-			    ctx->d_cnt, ctx->agg_dbg);
+			    ctx->d_cnt);
 			SYZ_HIP(hipGetLastError());
 			SYZ_TRY(counters_fetch(ctx));  // (synchronizes: rc is consumed)
 			if (ctx->h_cnt[kCntOverflow])
@@ -3092,7 +2937,7 @@ int agg_triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsi
 		k_agg_finalize<<<a.nregions, kFinThreads, 0, s>>>(
 		    a.dist_e, a.dist_f, a.cnt, a.nregions, lm, c0, ms->slots,
 		    ms->nbuckets - 1, nsp ? nsp->slots : nullptr, nsp ? nsp->nbuckets - 1 : 0, b->call_new, (uint64_t*)pr,
-		    &ctx->d_cnt[kCntAux2], ctx->d_cnt, ctx->agg_dbg);
+		    &ctx->d_cnt[kCntAux2], ctx->d_cnt);
 	}
 	SYZ_HIP(hipGetLastError());
 	if (ctx->timing)

@@ -229,7 +229,7 @@ struct syzsig_ctx {
 	bool agg_counted_once = false;        // the next agg_aggregate takes counted cells (a one-sync run spilled)
 	uint32_t edge_waves = 4;              // waves per program of k_edge_dedup (4 or 8; SYZSIG_EDGE_WAVES)
 	bool edge_mark_all = true;            // k_edge_dedup's marking mode for the next launch (edge.hip)
-	uint32_t agg_dbg = 0;                 // SYZSIG_DEBUG_* path flags; timing-only bits need -DSYZ_EXPERIMENTS
+	uint32_t agg_dbg = 0;                 // SYZSIG_DEBUG_* path flags (kDebugAccepted)
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	double last_ms = 0;                   // device time of the last timed entry point's kernels
 	// the stream-ordered sharded step (syzsig_step_*): its counters, read once by

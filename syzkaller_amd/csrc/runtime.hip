@@ -142,9 +142,8 @@ int syzsig_ctx_create(int device, syzsig_ctx** out)
 	if (const char* v = getenv("SYZSIG_AGG_DBG")) {
 		c->agg_dbg = (uint32_t)atoi(v);
 #ifndef SYZ_EXPERIMENTS
-		// timing-only bits (skipped merges, dropped records) exist only in an
-		// experiment build (make exp EXPFLAGS=-DSYZ_EXPERIMENTS): a stray variable
-		// can select the result-preserving debug paths and nothing else
+		// a stray variable selects the accepted debug paths and nothing else
+		// (kDebugAtomicFinalize: experiment builds only)
 		c->agg_dbg &= syz::kDebugAccepted;
 #endif
 	}

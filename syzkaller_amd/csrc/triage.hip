@@ -158,6 +158,10 @@ constexpr uint32_t kKnown = 0x80000000u;  // queue hint: slot index known from t
 // atomicMin of the record's level, and a run hint for later records of the
 // element.  The slow path thus runs dense and survivors never leave the chip;
 // the drain runs inside the segment loop so hints reach later segments.
+// dbg is always passed 0.  Its two bits are leftovers of timing experiments
+// and must stay unset: dbg & 1 drops every survivor (wrong results), dbg & 2
+// only skips the run hints.  (Taking the argument out changes the kernel's
+// register allocation, 80 -> 82 VGPRs: DESIGN.md section 8.)
 template <typename In, uint32_t kProbeU, uint32_t kDrain>
 __global__ __launch_bounds__(256) void k_probe(uint64_t* slots, uint64_t bmask, uint32_t* firsts, uint32_t* touched,
                                                In in, LevelMap lm, uint32_t epoch, uint32_t* cand_slot,

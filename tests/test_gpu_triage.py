@@ -206,7 +206,8 @@ def test_triage_cell_layouts(gpu, mode):
     record indices (SYZSIG_DEBUG_AGG_IDX64: the path of runs past record 2^32,
     both layouts), K2's marking-mode flag left set (SYZSIG_DEBUG_EDGE_PASSES:
     its bit once reached the scatter as a timing-only "drop the records"
-    switch), and a batch whose calls repeat one hot element hundreds of times, so that one cell of every
+    switch; that hook is gone, the scatter takes no debug flags), and a batch
+    whose calls repeat one hot element hundreds of times, so that one cell of every
     chunk overflows its capacity: each batch is redone with counted cells and
     the slack doubles until capped cells are given up -- every batch exact."""
     from syzkaller_amd import synth
@@ -252,6 +253,63 @@ def test_triage_cell_layouts(gpu, mode):
         gpu.eng.set_debug(0)
     assert st["parts"] >= 8 and st["overflow_parts"] == 0, st
     assert st["retries"] == (1 if mode == "spill" else 0), st
+
+
+SCAT3_TILE, SCAT3_FILL = 1024, 85  # agg.hip: kScat3Tile, kScat3Fill
+
+
+def scat3_takes(lens):
+    """agg.hip's split of a run's work items between its two capped scatters,
+    restated: k_scat3 places one call per tile of 1024 records and takes a
+    chunk whose tiles would be at least 85 % full; k_agg_scatter_blk the rest."""
+    recs = int(lens.sum(dtype=np.uint64))
+    tiles = int(((lens.astype(np.uint64) + SCAT3_TILE - 1) // SCAT3_TILE).sum())
+    return recs * 100 >= tiles * SCAT3_TILE * SCAT3_FILL
+
+
+def split_call_lengths(parts):
+    """Deterministic call lengths, about 2 M records, whose chunks (parts / 4
+    calls) fall on both sides of the fill rule.  A chunk repeats one pattern:
+    full tiles (with a zero-length call among them where a chunk has 4 calls or
+    more; at 2 calls per chunk the [2048, 0] chunks have it), half-empty second tiles,
+    two mixes one record either side of the bound ((1024 + L) * 100 >=
+    3 * 1024 * 85 <=> L >= 1588), zero-length and 1-record calls; the last
+    chunk is short."""
+    chunk = parts // 4
+    kinds = [[1024, 2048, 0, 1024], [1025, 1030], [1024, 1588], [1024, 1587], [0, 1], [0, 0], [1, 1], [2048, 0]]
+    if chunk > 2:  # 512 calls per chunk: 4 whole chunks and the short one
+        kinds = [kinds[0], kinds[1], kinds[2], [0, 1, 1, 0]]
+        reps, last = 1, [1024] * 64
+    else:
+        reps, last = 160, [1024]
+    lens = [np.resize(np.array(k, np.uint32), chunk) for _ in range(reps) for k in kinds] + [np.array(last, np.uint32)]
+    return np.concatenate(lens), chunk
+
+
+@pytest.mark.parametrize("parts", [8, 2048])
+def test_triage_scatter_split_by_tile_fill(gpu, parts):
+    """One capped-cell run whose chunks divide between k_scat3 (full one-call
+    tiles) and k_agg_scatter_blk (the rest), at 2 and at 512 calls per chunk,
+    exact against the oracle and without the counted-cell redo.  The library
+    reports no per-kernel item counts, so the split itself is asserted on the
+    restated rule only: a run in which one kernel took every item would still
+    have to be exact."""
+    hcnt, chunk = split_call_lengths(parts)
+    sides = [bool(scat3_takes(hcnt[i:i + chunk])) for i in range(0, hcnt.size, chunk)]
+    assert sides.count(True) >= 1 and sides.count(False) >= 1, sides
+    assert hcnt.size % chunk != 0 and (hcnt == 0).any() and (hcnt == 1).any()
+    rng = np.random.default_rng(parts)
+    # (few enough distinct elements per partition for k_agg's LDS table)
+    pool = rng.integers(0, 1 << 32, min(300_000, parts * 4000), dtype=np.uint64).astype(np.uint32)
+    hs = rng.choice(pool, int(hcnt.sum()))
+    hcs = (np.cumsum(hcnt, dtype=np.uint64) - hcnt).astype(np.uint64)
+    hprio = rng.integers(0, 4, hcnt.size).astype(np.uint8)
+    m0e = np.unique(rng.choice(pool, pool.size // 10))
+    m0 = (m0e, rng.integers(0, 4, m0e.size).astype(np.int8))
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(gpu.dev)  # noqa: E731
+    db = (t(hs, np.int32), t(hcs, np.int64), t(hcnt, np.int32), t(hprio, np.uint8))
+    st = compare(gpu, m0, (hs, hcs, hcnt, hprio), db, agg=2, parts=parts)
+    assert st["parts"] == parts and st["retries"] == 0 and st["overflow_parts"] == 0, st
 
 
 @pytest.mark.parametrize("over", [(0,) * 8, (1, 0, 0, 1, 0, 1, 1, 0), (1,) * 8])
