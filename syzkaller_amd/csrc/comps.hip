@@ -14,33 +14,16 @@
 // neighbours, write the survivors -- over keys of 3, 2 and 1 u64 words: the
 // comparison triple; the (key, value) pair of the map; a replacer.
 //
-// The segmented sort-unique is cover.hip's, templated on the key width W
-// (T = kCmTile keys, SYZSIG_COMPS_TILE):
-//   k_cm_small        one workgroup per segment of <= T keys: the keys into LDS
-//                     as W arrays of T words (a lane's compare reads one word
-//                     per array: consecutive lanes, consecutive 8-B words),
-//                     padded to a power of two with all-ones keys, bitonic
-//                     sort, then neighbour flags, block scan, compacted write.
-//                     8 W T bytes of LDS: 48 KB at W = 3.
-//   segments longer than T (a call has up to 65535 records, 131070 pairs) go
-//   through workspace buffers in HBM:
-//   k_cm_register     each gets a slot, a key range and its tiles (three
-//                     atomics per SEGMENT; none per key anywhere)
-//   k_cm_tile_sort    one workgroup per tile of T keys: sorted in LDS
-//   k_cm_merge        ceil(log2(tiles of the longest segment)) passes, known at
-//                     launch: runs of w keys merged pairwise by rank (left run:
-//                     lower bound in the right one; right run: upper bound in
-//                     the left one -- a bijection, duplicates included)
-//   k_cm_unique_large one workgroup per segment streams its sorted keys
-// What a survivor turns into is the output policy's business: CmOutKeys writes
-// the key itself; CmOutComps applies ignore() and write(), so a survivor
-// weighs 0, 3 or 5 output words, and the block scan runs over (count << 32 |
-// words).  Every loop is bounded by a segment length, a run count, a pass
-// count or the 64 steps of a binary search; nothing waits for another wave.
+// The segmented sort-unique is segsort.h's, over its plain tile of W-word keys
+// (T = kCmTile keys, SYZSIG_COMPS_TILE; 8 W T bytes of LDS, 48 KB at W = 3; a
+// call has up to 65535 records, 131070 pairs, so segments do pass T).  What a
+// survivor turns into is the output policy's business: SuOutKeys writes the
+// key itself; CmOutComps applies ignore() and write(), so a survivor weighs 0,
+// 3 or 5 output words, and the block scan runs over (count << 32 | words).
 #include <algorithm>
 #include <vector>
 
-#include "internal.h"
+#include "segsort.h"
 
 namespace syz {
 
@@ -48,7 +31,7 @@ namespace syz {
 #define SYZ_COMPS_TILE SYZSIG_COMPS_TILE
 #endif
 constexpr uint32_t kCmTile = SYZ_COMPS_TILE;
-constexpr uint32_t kCmThreads = 256;
+constexpr uint32_t kCmThreads = kSuThreads;
 constexpr uint32_t kCmMaxComps = 65535;       // executor.h:581-582: 8 + 32 n bytes fit kCoverSize * 8
 constexpr uint32_t kCmMaxSeg = 0x7fffffffu;   // keys per segment
 constexpr uint32_t kCmVariants = 12;          // hints.go:165-191: 7 widths little-endian, 5 big-endian (not at width 1)
@@ -58,64 +41,8 @@ constexpr uint32_t kCmpConst = 1, kCmpSizeMask = 6, kCmpSize1 = 0, kCmpSize2 = 2
 static_assert((kCmTile & (kCmTile - 1)) == 0 && kCmTile >= kCmThreads, "tile: a power of two, at least one sweep");
 static_assert(kCmTile * 3 * 8 <= 64 * 1024, "the widest key's tile stays at or below 64 KB of LDS");
 
-// the context's counters as this file uses them (zeroed per call)
-constexpr int kCmLarge = kCntAux, kCmTiles = kCntAux2, kCmKeys = kCntCandidates, kCmMaxLen = kCntTouched,
-              kCmCurLarge = kCntDefer, kCmCurTiles = kCntDeferNs, kCmCurKeys = kCntDistinct;
-
 template <int W>
-struct CmKey {
-	uint64_t w[W];
-};
-
-template <int W>
-__device__ __forceinline__ bool cm_lt(const CmKey<W>& a, const CmKey<W>& b)
-{
-#pragma unroll
-	for (int i = 0; i < W - 1; i++)
-		if (a.w[i] != b.w[i])
-			return a.w[i] < b.w[i];
-	return a.w[W - 1] < b.w[W - 1];
-}
-
-template <int W>
-__device__ __forceinline__ bool cm_eq(const CmKey<W>& a, const CmKey<W>& b)
-{
-	bool e = true;
-#pragma unroll
-	for (int i = 0; i < W; i++)
-		e = e && a.w[i] == b.w[i];
-	return e;
-}
-
-// Segment s is the concatenation of its R sources: the keys at src[(src_start[s
-// * R + r] + i) * stride .. + W), i < src_len[s * R + r]; seg_len[s] in all.
-struct CmSegs {
-	const uint64_t* src;
-	uint32_t stride;  // words from one key to the next (>= W)
-	const uint64_t* src_start;
-	const uint32_t* src_len;
-	uint32_t R;
-	const uint32_t* seg_len;
-	uint64_t nseg;
-};
-
-// output policy: the surviving keys themselves, segment s's at out[out_pos[s * pos_stride] * W ..]
-template <int W>
-struct CmOutKeys {
-	uint64_t* out;
-	const uint64_t* out_pos;  // in keys; segment s's is out_pos[s * pos_stride]
-	uint64_t pos_stride;
-	uint32_t* out_cnt;
-	__device__ __forceinline__ uint64_t weight(const CmKey<W>&) const { return 1; }
-	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const CmKey<W>& k) const
-	{
-		uint64_t* o = out + (out_pos[seg * pos_stride] + pos) * W;
-#pragma unroll
-		for (int i = 0; i < W; i++)
-			o[i] = k.w[i];
-	}
-	__device__ __forceinline__ void finish(uint64_t seg, uint64_t total) const { out_cnt[seg] = (uint32_t)total; }
-};
+using CmTile = SuWordsTile<W, kCmTile>;
 
 // output policy: executor.h:586-591 over the unique records -- ignore(), then write()
 struct CmOutComps {
@@ -147,7 +74,7 @@ struct CmOutComps {
 		return false;
 	}
 	// survivors << 32 | words
-	__device__ __forceinline__ uint64_t weight(const CmKey<3>& k) const
+	__device__ __forceinline__ uint64_t weight(const SuWords<3>& k) const
 	{
 		if (ignore(k.w[0], k.w[1], k.w[2]))
 			return 0;
@@ -155,7 +82,7 @@ struct CmOutComps {
 	}
 	// executor.h:823-859.  The low 32 bits of a sign extension from 1, 2 or 4
 	// bytes are what leaves for those sizes.
-	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const CmKey<3>& k) const
+	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const SuWords<3>& k) const
 	{
 		uint32_t* o = out + 5 * call_start[seg] + (uint32_t)pos;
 		const uint32_t sz = (uint32_t)k.w[0] & kCmpSizeMask;
@@ -188,26 +115,6 @@ struct CmOutComps {
 	}
 };
 
-// the segments longer than a tile, their key ranges in the sort buffers and
-// the tiles of all of them
-struct CmLarge {
-	const uint64_t* lg_seg;
-	const uint64_t* lg_base;  // in keys
-	const uint32_t* tile_lg;
-	const uint32_t* tile_idx;
-};
-
-__device__ __forceinline__ void cm_count_large(uint32_t len, uint64_t& nl, uint64_t& nt, uint64_t& nk,
-                                               unsigned long long* cnt)
-{
-	if (len > kCmTile) {
-		nl++;
-		nt += (len + kCmTile - 1) / kCmTile;
-		nk += len;
-		atomicMax(&cnt[kCmMaxLen], (unsigned long long)len);
-	}
-}
-
 // executor.h:578-582 per call: its records lie inside the buffer and are at
 // most 65535 (fail("too many comparisons")).  seg_len[c] = call_len[c].
 __global__ __launch_bounds__(256) void k_cm_prep_calls(const uint64_t* __restrict__ call_start,
@@ -224,13 +131,13 @@ __global__ __launch_bounds__(256) void k_cm_prep_calls(const uint64_t* __restric
 			seg_len[c] = 0;
 		} else {
 			seg_len[c] = len;
-			cm_count_large(len, nl, nt, nk, cnt);
+			su_count_large<kCmTile, 1>(len, nl, nt, nk, cnt);
 		}
 	}
 	block_count(&cnt[kCntError], err);
-	block_count(&cnt[kCmLarge], nl);
-	block_count(&cnt[kCmTiles], nt);
-	block_count(&cnt[kCmKeys], nk);
+	block_count(&cnt[kSuLarge], nl);
+	block_count(&cnt[kSuTiles], nt);
+	block_count(&cnt[kSuKeys], nk);
 }
 
 // seg_len[s] = the sum of its R source lengths (as a kernel left them)
@@ -248,342 +155,12 @@ __global__ __launch_bounds__(256) void k_cm_prep_sources(const uint32_t* __restr
 			total = 0;
 		}
 		seg_len[s] = (uint32_t)total;
-		cm_count_large((uint32_t)total, nl, nt, nk, cnt);
+		su_count_large<kCmTile, 1>((uint32_t)total, nl, nt, nk, cnt);
 	}
 	block_count(&cnt[kCntOverflow], ovf);
-	block_count(&cnt[kCmLarge], nl);
-	block_count(&cnt[kCmTiles], nt);
-	block_count(&cnt[kCmKeys], nk);
-}
-
-__device__ __forceinline__ uint64_t cm_wave_incl_scan(uint64_t v)
-{
-	const uint32_t lane = lane_id();
-#pragma unroll
-	for (uint32_t o = 1; o < 64; o <<= 1) {
-		const uint64_t x = __shfl_up(v, o, 64);
-		if (lane >= o)
-			v += x;
-	}
-	return v;
-}
-
-// off[0..n] = the exclusive prefix sums of v[0..n) (one workgroup)
-__global__ __launch_bounds__(kCmThreads) void k_cm_scan(const uint32_t* __restrict__ v, uint64_t n, uint64_t* off)
-{
-	__shared__ uint64_t s_w[kCmThreads / 64];
-	const uint32_t w = threadIdx.x >> 6;
-	uint64_t run = 0;
-	for (uint64_t base = 0; base < n; base += kCmThreads) {
-		const uint64_t i = base + threadIdx.x;
-		const uint64_t x = i < n ? v[i] : 0;
-		const uint64_t incl = cm_wave_incl_scan(x);
-		if (lane_id() == 63)
-			s_w[w] = incl;
-		__syncthreads();
-		uint64_t wb = 0, tot = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < kCmThreads / 64; k++) {
-			wb += k < w ? s_w[k] : 0;
-			tot += s_w[k];
-		}
-		if (i < n)
-			off[i] = run + wb + incl - x;
-		run += tot;
-		__syncthreads();
-	}
-	if (threadIdx.x == 0)
-		off[n] = run;
-}
-
-// the tile in LDS: W arrays of kCmTile words
-template <int W>
-struct CmTileLds {
-	uint64_t k[W][kCmTile];
-	__device__ __forceinline__ CmKey<W> get(uint32_t i) const
-	{
-		CmKey<W> x;
-#pragma unroll
-		for (int w = 0; w < W; w++)
-			x.w[w] = k[w][i];
-		return x;
-	}
-	__device__ __forceinline__ void set(uint32_t i, const CmKey<W>& x)
-	{
-#pragma unroll
-		for (int w = 0; w < W; w++)
-			k[w][i] = x.w[w];
-	}
-};
-
-// t[0 .. n) = the keys [lo, lo + n) of segment `seg` (workgroup-wide)
-template <int W>
-__device__ __forceinline__ void cm_load(const CmSegs& S, uint64_t seg, uint32_t lo, uint32_t n, CmTileLds<W>& t)
-{
-	uint64_t o = 0;
-	for (uint32_t r = 0; r < S.R; r++) {
-		const uint32_t len = S.src_len[seg * S.R + r];
-		const uint64_t a = std::max<uint64_t>(lo, o), b = std::min<uint64_t>((uint64_t)lo + n, o + len);
-		if (a < b) {
-			const uint64_t* p = S.src + (S.src_start[seg * S.R + r] + (a - o)) * S.stride;
-			const uint32_t d = (uint32_t)(a - lo), cnt = (uint32_t)(b - a);
-			for (uint32_t i = threadIdx.x; i < cnt; i += kCmThreads) {
-#pragma unroll
-				for (int w = 0; w < W; w++)
-					t.k[w][d + i] = p[(uint64_t)i * S.stride + w];
-			}
-		}
-		o += len;
-	}
-}
-
-// Bitonic sort of t[0 .. N) ascending; N a power of two <= kCmTile.  Starts and
-// ends with a barrier.
-template <int W>
-__device__ __forceinline__ void cm_sort(CmTileLds<W>& t, uint32_t N)
-{
-	for (uint32_t size = 2; size <= N; size <<= 1) {
-		for (uint32_t st = size >> 1; st > 0; st >>= 1) {
-			__syncthreads();
-			for (uint32_t x = threadIdx.x; x < N / 2; x += kCmThreads) {
-				const uint32_t i = 2 * x - (x & (st - 1)), j = i + st;
-				const bool asc = (i & size) == 0;
-				const CmKey<W> a = t.get(i), b = t.get(j);
-				if (asc ? cm_lt(b, a) : cm_lt(a, b)) {
-					t.set(i, b);
-					t.set(j, a);
-				}
-			}
-		}
-	}
-	__syncthreads();
-}
-
-// The survivors of the sorted keys 0 .. n) -- key i survives iff i == 0 or it
-// differs from key i - 1 -- handed to the policy at the exclusive sums of their
-// weights; returns the total (workgroup-wide, uniform).
-template <int W, typename Pol, typename Get>
-__device__ __forceinline__ uint64_t cm_unique_write(uint32_t n, uint64_t seg, const Pol& pol, Get get)
-{
-	__shared__ uint64_t s_w[2][kCmThreads / 64];
-	const uint32_t tid = threadIdx.x, w = tid >> 6;
-	uint64_t run = 0;
-	uint32_t it = 0;
-	for (uint32_t base = 0; base < n; base += kCmThreads, it ^= 1) {
-		const uint32_t i = base + tid;
-		CmKey<W> k = {};
-		uint64_t wt = 0;
-		if (i < n) {
-			k = get(i);
-			if (i == 0 || !cm_eq(k, get(i - 1)))
-				wt = pol.weight(k);
-		}
-		const uint64_t incl = cm_wave_incl_scan(wt);
-		if (lane_id() == 63)
-			s_w[it][w] = incl;
-		__syncthreads();  // (s_w[it] is rewritten two sweeps on, past the next sweep's barrier)
-		uint64_t wb = 0, tot = 0;
-#pragma unroll
-		for (uint32_t x = 0; x < kCmThreads / 64; x++) {
-			wb += x < w ? s_w[it][x] : 0;
-			tot += s_w[it][x];
-		}
-		if (wt)
-			pol.put(seg, run + wb + incl - wt, k);
-		run += tot;
-	}
-	return run;
-}
-
-__device__ __forceinline__ uint32_t cm_pow2(uint32_t n)
-{
-	uint32_t N = 1;
-	while (N < n)
-		N <<= 1;
-	return N;
-}
-
-template <int W>
-__device__ __forceinline__ void cm_pad(CmTileLds<W>& t, uint32_t n, uint32_t N)
-{
-	CmKey<W> pad;
-#pragma unroll
-	for (int w = 0; w < W; w++)
-		pad.w[w] = ~0ull;
-	for (uint32_t i = n + threadIdx.x; i < N; i += kCmThreads)
-		t.set(i, pad);  // (>= every key: the first n sorted keys are the segment's)
-}
-
-template <int W, typename Pol>
-__global__ __launch_bounds__(kCmThreads) void k_cm_small(CmSegs S, Pol pol)
-{
-	__shared__ CmTileLds<W> t;
-	for (uint64_t seg = blockIdx.x; seg < S.nseg; seg += gridDim.x) {
-		const uint32_t n = S.seg_len[seg];
-		if (n > kCmTile)
-			continue;  // k_cm_unique_large finishes it
-		if (n == 0) {
-			if (threadIdx.x == 0)
-				pol.finish(seg, 0);
-			continue;
-		}
-		const uint32_t N = cm_pow2(n);  // <= kCmTile
-		cm_load<W>(S, seg, 0, n, t);
-		cm_pad<W>(t, n, N);
-		cm_sort<W>(t, N);
-		const uint64_t c = cm_unique_write<W>(n, seg, pol, [&](uint32_t i) { return t.get(i); });
-		if (threadIdx.x == 0)
-			pol.finish(seg, c);
-		__syncthreads();  // t is refilled for the next segment
-	}
-}
-
-// Every segment longer than a tile takes a slot, a key range and its tiles.
-// The capacities are the counts the prep kernel took over the same lengths, so
-// the checks cannot fail; they keep a write inside its array whatever happens.
-__global__ __launch_bounds__(256) void k_cm_register(const uint32_t* __restrict__ seg_len, uint64_t nseg,
-                                                     uint64_t cap_large, uint64_t cap_tiles, uint64_t cap_keys,
-                                                     uint64_t* lg_seg, uint64_t* lg_base, uint32_t* tile_lg,
-                                                     uint32_t* tile_idx, unsigned long long* cnt)
-{
-	const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (s >= nseg)
-		return;
-	const uint32_t len = seg_len[s];
-	if (len <= kCmTile)
-		return;
-	const uint32_t nt = (len + kCmTile - 1) / kCmTile;
-	const uint64_t L = atomicAdd(&cnt[kCmCurLarge], 1ull), tb = atomicAdd(&cnt[kCmCurTiles], (unsigned long long)nt),
-	               kb = atomicAdd(&cnt[kCmCurKeys], (unsigned long long)len);
-	if (L >= cap_large || tb + nt > cap_tiles || kb + len > cap_keys) {
-		atomicAdd(&cnt[kCntError], 1ull);
-		return;
-	}
-	lg_seg[L] = s;
-	lg_base[L] = kb;
-	for (uint32_t t = 0; t < nt; t++) {
-		tile_lg[tb + t] = (uint32_t)L;
-		tile_idx[tb + t] = t;
-	}
-}
-
-// the sort buffers hold a key's W words side by side
-template <int W>
-__device__ __forceinline__ CmKey<W> cm_buf_get(const uint64_t* __restrict__ p, uint64_t i)
-{
-	CmKey<W> x;
-#pragma unroll
-	for (int w = 0; w < W; w++)
-		x.w[w] = p[i * W + w];
-	return x;
-}
-
-template <int W>
-__global__ __launch_bounds__(kCmThreads) void k_cm_tile_sort(CmSegs S, CmLarge G, uint64_t ntiles, uint64_t* buf,
-                                                              const unsigned long long* cnt)
-{
-	__shared__ CmTileLds<W> t;
-	if (cnt[kCntError])
-		return;  // k_cm_register left a table unwritten: the call fails, nothing reads it
-	for (uint64_t b = blockIdx.x; b < ntiles; b += gridDim.x) {
-		const uint32_t L = G.tile_lg[b];
-		const uint64_t seg = G.lg_seg[L];
-		const uint32_t len = S.seg_len[seg], lo = G.tile_idx[b] * kCmTile;
-		const uint32_t n = len - lo < kCmTile ? len - lo : kCmTile, N = cm_pow2(n);
-		cm_load<W>(S, seg, lo, n, t);
-		cm_pad<W>(t, n, N);
-		cm_sort<W>(t, N);
-		uint64_t* o = buf + (G.lg_base[L] + lo) * W;
-		for (uint32_t i = threadIdx.x; i < n; i += kCmThreads) {
-			const CmKey<W> x = t.get(i);
-#pragma unroll
-			for (int w = 0; w < W; w++)
-				o[(uint64_t)i * W + w] = x.w[w];
-		}
-		__syncthreads();
-	}
-}
-
-// the first index in [lo, hi) of the sorted keys p whose key is >= x (kUpper: > x)
-template <int W, bool kUpper>
-__device__ __forceinline__ uint64_t cm_bound(const uint64_t* __restrict__ p, uint64_t lo, uint64_t hi,
-                                             const CmKey<W>& x)
-{
-	for (uint32_t it = 0; it < 32 && lo < hi; it++) {  // hi - lo < 2^31 halves every step
-		const uint64_t mid = lo + ((hi - lo) >> 1);
-		const CmKey<W> v = cm_buf_get<W>(p, mid);
-		if (kUpper ? !cm_lt(x, v) : cm_lt(v, x))
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-// one merge pass: sorted runs of w keys -> sorted runs of 2 w keys
-template <int W>
-__global__ __launch_bounds__(kCmThreads) void k_cm_merge(const uint32_t* __restrict__ seg_len, CmLarge G,
-                                                          uint64_t ntiles, uint64_t w,
-                                                          const uint64_t* __restrict__ src, uint64_t* dst,
-                                                          const unsigned long long* cnt)
-{
-	if (cnt[kCntError])
-		return;
-	for (uint64_t b = blockIdx.x; b < ntiles; b += gridDim.x) {
-		const uint32_t L = G.tile_lg[b];
-		const uint64_t len = seg_len[G.lg_seg[L]], lo = (uint64_t)G.tile_idx[b] * kCmTile;
-		const uint64_t n = len - lo < kCmTile ? len - lo : kCmTile;
-		const uint64_t* s = src + G.lg_base[L] * W;
-		uint64_t* d = dst + G.lg_base[L] * W;
-		// a tile lies inside one run (w is a multiple of the tile): uniform per workgroup
-		const uint64_t pb = lo / (2 * w) * (2 * w), a1 = std::min(pb + w, len), b1 = std::min(pb + 2 * w, len);
-		const bool left = lo < a1;
-		for (uint64_t li = lo + threadIdx.x; li < lo + n; li += kCmThreads) {
-			const CmKey<W> x = cm_buf_get<W>(s, li);
-			const uint64_t pos = left ? li + (cm_bound<W, false>(s, a1, b1, x) - a1)
-			                          : pb + (li - a1) + (cm_bound<W, true>(s, pb, a1, x) - pb);
-#pragma unroll
-			for (int q = 0; q < W; q++)
-				d[pos * W + q] = x.w[q];
-		}
-	}
-}
-
-template <int W, typename Pol>
-__global__ __launch_bounds__(kCmThreads) void k_cm_unique_large(CmSegs S, CmLarge G, uint64_t nlarge,
-                                                                 const uint64_t* __restrict__ buf, Pol pol,
-                                                                 const unsigned long long* cnt)
-{
-	if (cnt[kCntError])
-		return;
-	for (uint64_t L = blockIdx.x; L < nlarge; L += gridDim.x) {
-		const uint64_t seg = G.lg_seg[L];
-		const uint32_t n = S.seg_len[seg];
-		const uint64_t* s = buf + G.lg_base[L] * W;
-		const uint64_t c = cm_unique_write<W>(n, seg, pol, [&](uint32_t i) { return cm_buf_get<W>(s, i); });
-		if (threadIdx.x == 0)
-			pol.finish(seg, c);
-		__syncthreads();
-	}
-}
-
-// segment i's sorted keys from the staging buffer to their place in the output
-template <int W>
-__global__ __launch_bounds__(kCmThreads) void k_cm_gather(const uint64_t* __restrict__ stage,
-                                                           const uint64_t* __restrict__ stage_pos,
-                                                           uint64_t pos_stride, const uint64_t* __restrict__ off,
-                                                           uint64_t nseg, uint64_t* out, uint64_t* out_off)
-{
-	for (uint64_t i = blockIdx.x; i < nseg; i += gridDim.x) {
-		const uint64_t a = off[i], n = (off[i + 1] - a) * W;
-		const uint64_t* s = stage + stage_pos[i * pos_stride] * W;
-		for (uint64_t x = threadIdx.x; x < n; x += kCmThreads)
-			out[a * W + x] = s[x];
-		if (threadIdx.x == 0)
-			out_off[i] = a;
-	}
-	if (blockIdx.x == 0 && threadIdx.x == 0)
-		out_off[nseg] = off[nseg];
+	block_count(&cnt[kSuLarge], nl);
+	block_count(&cnt[kSuTiles], nt);
+	block_count(&cnt[kSuKeys], nk);
 }
 
 // ---- syzsig_comp_map_dev ----
@@ -728,25 +305,11 @@ __global__ __launch_bounds__(256) void k_se_count(const uint64_t* __restrict__ m
 			bool expand, be;
 			cm_variant(x, width, expand, be);
 			const uint64_t m = cm_mutant(q_val[q], width, expand, be);
-			uint64_t lo = a, hi = b;  // the first pair with key >= m
-			for (uint32_t it = 0; it < 32 && lo < hi; it++) {
-				const uint64_t mid = lo + ((hi - lo) >> 1);
-				if (pairs[2 * mid] < m)
-					lo = mid + 1;
-				else
-					hi = mid;
-			}
-			const uint64_t first = lo;
-			hi = b;  // the first pair with key > m
-			for (uint32_t it = 0; it < 32 && lo < hi; it++) {
-				const uint64_t mid = lo + ((hi - lo) >> 1);
-				if (pairs[2 * mid] <= m)
-					lo = mid + 1;
-				else
-					hi = mid;
-			}
+			// the first pair with key >= m, then from there the first with key > m
+			const uint64_t first = su_search(a, b, [&](uint64_t i) { return pairs[2 * i] < m; });
+			const uint64_t past = su_search(first, b, [&](uint64_t i) { return pairs[2 * i] <= m; });
 			vlo[g] = first;
-			vcnt[g] = (uint32_t)(lo - first);
+			vcnt[g] = (uint32_t)(past - first);
 		}
 	}
 	block_count(&cnt[kCntError], err);
@@ -754,14 +317,7 @@ __global__ __launch_bounds__(256) void k_se_count(const uint64_t* __restrict__ m
 
 __device__ __forceinline__ bool cm_is_special(const uint64_t* __restrict__ sp, uint32_t nsp, uint64_t v)
 {
-	uint32_t lo = 0, hi = nsp;
-	for (uint32_t it = 0; it < 32 && lo < hi; it++) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (sp[mid] < v)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
+	const uint32_t lo = su_search(0u, nsp, [&](uint32_t i) { return sp[i] < v; });
 	return lo < nsp && sp[lo] == v;
 }
 
@@ -813,56 +369,6 @@ __global__ __launch_bounds__(256) void k_se_write(const uint64_t* __restrict__ p
 	}
 }
 
-static size_t cm_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static int cm_grid(uint64_t n) { return (int)std::min<uint64_t>(std::max<uint64_t>(n, 1), 1u << 20); }
-
-// The sort-unique of every segment of S (lengths and counts as the prep
-// kernel left them in ctx->h_cnt).  Enqueues only.
-template <int W, typename Pol>
-static int cm_sort_unique(syzsig_ctx* ctx, const CmSegs& S, const Pol& pol)
-{
-	const hipStream_t s = ctx->stream;
-	const uint64_t nlarge = ctx->h_cnt[kCmLarge], ntiles = ctx->h_cnt[kCmTiles], nkeys = ctx->h_cnt[kCmKeys],
-	               maxlen = ctx->h_cnt[kCmMaxLen];
-	k_cm_small<W, Pol><<<cm_grid(S.nseg), kCmThreads, 0, s>>>(S, pol);
-	if (nlarge) {
-		char* tab;
-		void *ba, *bb;
-		const size_t o_base = cm_align(nlarge * 8), o_tlg = o_base + cm_align(nlarge * 8),
-		             o_tix = o_tlg + cm_align(ntiles * 4);
-		SYZ_TRY(ws_get(ctx, kWsSuTab, o_tix + cm_align(ntiles * 4), (void**)&tab));
-		SYZ_TRY(ws_get(ctx, kWsSuBufA, nkeys * 8 * W + 256, &ba));
-		SYZ_TRY(ws_get(ctx, kWsSuBufB, nkeys * 8 * W + 256, &bb));
-		uint64_t* lg_seg = (uint64_t*)tab;
-		uint64_t* lg_base = (uint64_t*)(tab + o_base);
-		uint32_t* tile_lg = (uint32_t*)(tab + o_tlg);
-		uint32_t* tile_idx = (uint32_t*)(tab + o_tix);
-		k_cm_register<<<(int)((S.nseg + 255) / 256), 256, 0, s>>>(S.seg_len, S.nseg, nlarge, ntiles, nkeys, lg_seg,
-		                                                          lg_base, tile_lg, tile_idx, ctx->d_cnt);
-		const CmLarge G{lg_seg, lg_base, tile_lg, tile_idx};
-		uint64_t *src = (uint64_t*)ba, *dst = (uint64_t*)bb;
-		k_cm_tile_sort<W><<<cm_grid(ntiles), kCmThreads, 0, s>>>(S, G, ntiles, src, ctx->d_cnt);
-		for (uint64_t w = kCmTile; w < maxlen; w <<= 1) {
-			k_cm_merge<W><<<cm_grid(ntiles), kCmThreads, 0, s>>>(S.seg_len, G, ntiles, w, src, dst, ctx->d_cnt);
-			std::swap(src, dst);
-		}
-		k_cm_unique_large<W, Pol><<<cm_grid(nlarge), kCmThreads, 0, s>>>(S, G, nlarge, src, pol, ctx->d_cnt);
-	}
-	SYZ_HIP(hipGetLastError());
-	return SYZSIG_OK;
-}
-
-static int cm_finish_timing(syzsig_ctx* ctx)
-{
-	if (ctx->timing) {
-		float t = 0;
-		SYZ_HIP(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-		ctx->last_ms = t;
-	}
-	return SYZSIG_OK;
-}
-
 // The tail the two CSR entry points share: the segments' survivors lie in
 // `stage` (segment i's at stage_pos[i * pos_stride], cnt[i] of them); their
 // offsets, the capacity check and the gather.
@@ -873,7 +379,7 @@ static int cm_emit_csr(syzsig_ctx* ctx, const char* what, const uint64_t* stage,
                        const int32_t* status = nullptr)
 {
 	const hipStream_t s = ctx->stream;
-	k_cm_scan<<<1, kCmThreads, 0, s>>>(cnt, nseg, off);
+	k_su_scan<<<1, kCmThreads, 0, s>>>(cnt, nseg, off);
 	SYZ_HIP(hipGetLastError());
 	uint64_t total = 0;
 	SYZ_HIP(hipMemcpyAsync(&total, off + nseg, 8, hipMemcpyDeviceToHost, s));
@@ -883,14 +389,13 @@ static int cm_emit_csr(syzsig_ctx* ctx, const char* what, const uint64_t* stage,
 	*n_out = total;
 	if (total > cap)
 		return fail(SYZSIG_ERANGE, std::string(what) + ": the result needs more than the given capacity");
-	k_cm_gather<W><<<cm_grid(nseg), kCmThreads, 0, s>>>(stage, stage_pos, pos_stride, off, nseg, d_out, d_off);
+	k_su_gather<<<grid_cap(nseg), kCmThreads, 0, s>>>(stage, stage_pos, pos_stride, W, off, nseg, d_out, d_off);
 	SYZ_HIP(hipGetLastError());
 	if (d_status)
 		SYZ_HIP(hipMemcpyAsync(d_status, status, nseg * 4, hipMemcpyDeviceToDevice, s));
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
+	SYZ_TRY(su_time_end(ctx));
 	SYZ_HIP(hipStreamSynchronize(s));
-	return cm_finish_timing(ctx);
+	return SYZSIG_OK;
 }
 
 }  // namespace syz
@@ -914,8 +419,7 @@ extern "C" int syzsig_exec_comps_dev(syzsig_ctx* ctx, const uint64_t* d_comps, u
 	void* seg_len;
 	SYZ_TRY(ws_get(ctx, kWsSuMeta, ncalls * 4 + 256, &seg_len));
 	SYZ_TRY(counters_reset(ctx));
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
+	SYZ_TRY(su_time_begin(ctx));
 	k_cm_prep_calls<<<(int)((ncalls + 255) / 256), 256, 0, s>>>(d_call_start, d_call_len, ncalls, ncmp,
 	                                                            (uint32_t*)seg_len, ctx->d_cnt);
 	SYZ_HIP(hipGetLastError());
@@ -923,13 +427,11 @@ extern "C" int syzsig_exec_comps_dev(syzsig_ctx* ctx, const uint64_t* d_comps, u
 	if (ctx->h_cnt[kCntError])
 		return fail(SYZSIG_EINVAL, "exec_comps: a call's records lie outside the buffer, or a call has more than "
 		                           "65535 comparisons");
-	const CmSegs S{d_comps, 4, d_call_start, (const uint32_t*)seg_len, 1, (const uint32_t*)seg_len, ncalls};
+	const SuSegs S{d_comps, 4, d_call_start, (const uint32_t*)seg_len, 1, (const uint32_t*)seg_len, ncalls};
 	const CmOutComps pol{d_out, d_call_start, d_out_words, d_comps_cnt, out_start};
-	SYZ_TRY((cm_sort_unique<3, CmOutComps>(ctx, S, pol)));
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
+	SYZ_TRY((su_sort_unique<CmTile<3>, CmOutComps>(ctx, S, pol)));
+	SYZ_TRY(su_time_end(ctx));
 	SYZ_TRY(counters_fetch(ctx));
-	SYZ_TRY(cm_finish_timing(ctx));
 	if (ctx->h_cnt[kCntError])
 		return fail(SYZSIG_EIO, "exec_comps: internal: a long segment did not fit its workspace");
 	return SYZSIG_OK;
@@ -955,15 +457,14 @@ extern "C" int syzsig_comp_map_dev(syzsig_ctx* ctx, const uint32_t* d_words, uin
 	// rec_base[ncalls + 1], pair_start[ncalls], pair_len[ncalls], seg_len[ncalls], cnt[ncalls], off[ncalls + 1],
 	// status[ncalls] (nothing of the caller's is written before the capacity check)
 	char* d;
-	const size_t o_ps = cm_align((ncalls + 1) * 8), o_pl = o_ps + cm_align(ncalls * 8), o_sl = o_pl + cm_align(ncalls * 4),
-	             o_cnt = o_sl + cm_align(ncalls * 4), o_off = o_cnt + cm_align(ncalls * 4), o_st = o_off + cm_align((ncalls + 1) * 8);
-	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_st + cm_align(ncalls * 4), (void**)&d));
+	const size_t o_ps = align256((ncalls + 1) * 8), o_pl = o_ps + align256(ncalls * 8), o_sl = o_pl + align256(ncalls * 4),
+	             o_cnt = o_sl + align256(ncalls * 4), o_off = o_cnt + align256(ncalls * 4), o_st = o_off + align256((ncalls + 1) * 8);
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_st + align256(ncalls * 4), (void**)&d));
 	uint64_t *rec_base = (uint64_t*)d, *pair_start = (uint64_t*)(d + o_ps), *off = (uint64_t*)(d + o_off);
 	uint32_t *pair_len = (uint32_t*)(d + o_pl), *seg_len = (uint32_t*)(d + o_sl), *cnt = (uint32_t*)(d + o_cnt);
 	int32_t* status = (int32_t*)(d + o_st);
 	SYZ_TRY(counters_reset(ctx));
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
+	SYZ_TRY(su_time_begin(ctx));
 	const int cb = (int)((ncalls + 255) / 256);
 	k_cm_check_regions<<<cb, 256, 0, s>>>(d_comps_start, d_comps_cnt, d_comps_end, ncalls, nwords, ctx->d_cnt);
 	SYZ_HIP(hipGetLastError());
@@ -971,7 +472,7 @@ extern "C" int syzsig_comp_map_dev(syzsig_ctx* ctx, const uint32_t* d_words, uin
 	if (ctx->h_cnt[kCntError])
 		return fail(SYZSIG_EINVAL, "comp_map: a call's comparisons start outside its region, a region ends outside "
 		                           "the buffer, or a call has more than 65535 comparisons");
-	k_cm_scan<<<1, kCmThreads, 0, s>>>(d_comps_cnt, ncalls, rec_base);
+	k_su_scan<<<1, kCmThreads, 0, s>>>(d_comps_cnt, ncalls, rec_base);
 	SYZ_HIP(hipGetLastError());
 	uint64_t nrec = 0;
 	SYZ_HIP(hipMemcpyAsync(&nrec, rec_base + ncalls, 8, hipMemcpyDeviceToHost, s));
@@ -985,9 +486,9 @@ extern "C" int syzsig_comp_map_dev(syzsig_ctx* ctx, const uint32_t* d_words, uin
 	k_cm_prep_sources<<<cb, 256, 0, s>>>(pair_len, 1, ncalls, seg_len, ctx->d_cnt);
 	SYZ_HIP(hipGetLastError());
 	SYZ_TRY(counters_fetch(ctx));
-	const CmSegs S{(const uint64_t*)stage, 2, pair_start, pair_len, 1, seg_len, ncalls};
-	const CmOutKeys<2> pol{(uint64_t*)stage2, pair_start, 1, cnt};
-	SYZ_TRY((cm_sort_unique<2, CmOutKeys<2>>(ctx, S, pol)));
+	const SuSegs S{stage, 2, pair_start, pair_len, 1, seg_len, ncalls};
+	const SuOutKeys<SuU64<2>> pol{(uint64_t*)stage2, pair_start, 1, cnt};
+	SYZ_TRY((su_sort_unique<CmTile<2>, SuOutKeys<SuU64<2>>>(ctx, S, pol)));
 	return cm_emit_csr<2>(ctx, "comp_map", (const uint64_t*)stage2, pair_start, 1, cnt, off, ncalls, d_map_off,
 	                      d_pairs, cap, n_out, d_status, status);
 }
@@ -1017,10 +518,10 @@ extern "C" int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_o
 	const uint64_t nv = nq * kCmVariants;
 	// vlo[nv], voff[nv + 1], vcnt[nv], src_len[nv], seg_len[nq], cnt[nq], off[nq + 1], special[nspecial]
 	char* d;
-	const size_t o_voff = cm_align(nv * 8), o_vcnt = o_voff + cm_align((nv + 1) * 8), o_sl = o_vcnt + cm_align(nv * 4),
-	             o_seg = o_sl + cm_align(nv * 4), o_cnt = o_seg + cm_align(nq * 4), o_off = o_cnt + cm_align(nq * 4),
-	             o_sp = o_off + cm_align((nq + 1) * 8);
-	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_sp + cm_align((size_t)nspecial * 8 + 8), (void**)&d));
+	const size_t o_voff = align256(nv * 8), o_vcnt = o_voff + align256((nv + 1) * 8), o_sl = o_vcnt + align256(nv * 4),
+	             o_seg = o_sl + align256(nv * 4), o_cnt = o_seg + align256(nq * 4), o_off = o_cnt + align256(nq * 4),
+	             o_sp = o_off + align256((nq + 1) * 8);
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_sp + align256((size_t)nspecial * 8 + 8), (void**)&d));
 	uint64_t *vlo = (uint64_t*)d, *voff = (uint64_t*)(d + o_voff), *off = (uint64_t*)(d + o_off),
 	         *special = (uint64_t*)(d + o_sp);
 	uint32_t *vcnt = (uint32_t*)(d + o_vcnt), *src_len = (uint32_t*)(d + o_sl), *seg_len = (uint32_t*)(d + o_seg),
@@ -1032,11 +533,10 @@ extern "C" int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_o
 		SYZ_HIP(hipMemcpyAsync(special, sp.data(), (size_t)nspecial * 8, hipMemcpyHostToDevice, s));
 		SYZ_HIP(hipStreamSynchronize(s));
 	}
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
+	SYZ_TRY(su_time_begin(ctx));
 	k_se_count<<<(int)((nv + 255) / 256), 256, 0, s>>>(d_map_off, d_pairs, ncalls, npairs, d_q_call, d_q_val, nq, vlo,
 	                                                   vcnt, ctx->d_cnt);
-	k_cm_scan<<<1, kCmThreads, 0, s>>>(vcnt, nv, voff);
+	k_su_scan<<<1, kCmThreads, 0, s>>>(vcnt, nv, voff);
 	SYZ_HIP(hipGetLastError());
 	uint64_t ncand = 0;
 	SYZ_HIP(hipMemcpyAsync(&ncand, voff + nv, 8, hipMemcpyDeviceToHost, s));
@@ -1054,10 +554,10 @@ extern "C" int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_o
 	SYZ_TRY(counters_fetch(ctx));
 	if (ctx->h_cnt[kCntOverflow])
 		return fail(SYZSIG_ERANGE, "shrink_expand: a query has 2^31 or more candidates");
-	const CmSegs S{(const uint64_t*)cand, 1, voff, src_len, kCmVariants, seg_len, nq};
+	const SuSegs S{cand, 1, voff, src_len, kCmVariants, seg_len, nq};
 	// a query's survivors go to the head of its own candidate range in stage2
-	const CmOutKeys<1> pol{(uint64_t*)stage2, voff, kCmVariants, cnt};
-	SYZ_TRY((cm_sort_unique<1, CmOutKeys<1>>(ctx, S, pol)));
+	const SuOutKeys<SuU64<1>> pol{(uint64_t*)stage2, voff, kCmVariants, cnt};
+	SYZ_TRY((su_sort_unique<CmTile<1>, SuOutKeys<SuU64<1>>>(ctx, S, pol)));
 	return cm_emit_csr<1>(ctx, "shrink_expand", (const uint64_t*)stage2, voff, kCmVariants, cnt, off, nq,
 	                      d_rep_off, d_rep, cap, n_out);
 }

@@ -23,11 +23,11 @@
 //   k_ni_rows / rp_group   the non-PRESENT entries, e << 32 | entry index,
 //                          grouped by element through the LDS partitions of
 //                          recs.hip
-//   k_ni_walk              k_poll_part_walk's sibling: one workgroup per
-//                          partition sorts its entries by (element, entry
-//                          index) in LDS, one thread per element run emits the
-//                          events and marks their rows accepted (read-only on
-//                          corpusSignal)
+//   k_ni_walk              segsort.h's su_sort_walk, as k_poll_part_walk: one
+//                          workgroup per partition sorts its entries by
+//                          (element, entry index) in LDS, one thread per element
+//                          run emits the events; here an event also marks its
+//                          row accepted (read-only on corpusSignal)
 //   k_ni_commit            corpusSignal.Merge of the events and, flagged by
 //                          `accepted`, every accepted row's cover into
 //                          corpusCover -- one launch, after every allocation
@@ -38,61 +38,32 @@
 // arrival order (host), then
 //   k_ni_gather            keys elem << 32 | index-in-group, and per entry its
 //                          row and prio
-//   k_ni_tile_sort         one workgroup per tile of kNiTile keys: bitonic in LDS
-//   k_ni_merge             ceil(log2(tiles of the longest group)) rank-merge
-//                          passes (cover.hip's k_cover_merge over u64); keys are
-//                          distinct, a group of one tile is copied through
+//   k_su_tile_sort, k_su_merge   segsort.h's tile sort (tiles of kNiTile keys)
+//                          and rank-merge passes over a tile table built on the
+//                          host; keys are distinct
 //   k_ni_reduce            one workgroup per group streams its sorted keys: per
 //                          run of one element, per row the last entry
 //                          (Deserialize), the max over rows (Merge), block scan,
 //                          compacted write
-//   k_ni_csr               the groups' results packed into the CSR output
-// and the covers through cover.hip's segmented sort-unique
+//   k_su_gather            the groups' results packed into the CSR output
+// and the covers through cover.hip's instance of the segmented sort-unique
 // (syzsig_triage_cover_dev, one run per group).  No device atomic per entry;
 // every loop is bounded by a group, run or tile length known at launch.
 #include <algorithm>
 #include <chrono>
 #include <vector>
 
-#include "internal.h"
+#include "segsort.h"
 
 namespace syz {
 
 constexpr uint64_t kNiMaxEntries = 1ull << 23;  // entries of one batched acceptance (the element partitions' capacity)
 constexpr uint32_t kNiTile = SYZSIG_CORPUS_TILE;
-constexpr uint32_t kNiThreads = 256;
-constexpr uint64_t kNiPad = ~0ull;
+constexpr uint32_t kNiThreads = kSuThreads;
+constexpr uint64_t kNiMaxGrid = 1u << 16;
 constexpr int kNiCovIns = kCntAux2;  // PCs new to corpusCover (kCntInserted counts corpusSignal's)
 static_assert((kNiTile & (kNiTile - 1)) == 0 && kNiTile >= 2 && kNiTile * 8 <= 64 * 1024, "tile: a power of two in LDS");
-
-// Bitonic sort of k[0 .. N) ascending, N a power of two >= 2 (workgroup-wide;
-// the fill needs no barrier of its own, ends with one).
-__device__ __forceinline__ void ni_sort(uint64_t* k, uint32_t N)
-{
-	const uint32_t tid = threadIdx.x;
-	for (uint32_t size = 2; size <= N; size <<= 1) {
-		for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-			__syncthreads();
-			for (uint32_t t = tid; t < N / 2; t += kNiThreads) {
-				const uint32_t i = 2 * t - (t & (stride - 1)), j = i + stride;
-				const uint64_t a = k[i], b = k[j];
-				if ((a > b) == ((i & size) == 0)) {
-					k[i] = b;
-					k[j] = a;
-				}
-			}
-		}
-	}
-	__syncthreads();
-}
-
-__device__ __forceinline__ uint32_t ni_pow2(uint32_t n)
-{
-	uint32_t N = 2;
-	while (N < n)
-		N <<= 1;
-	return N;
-}
+using NiTile = SuWordsTile<1, kNiTile>;
 
 // Acceptance row j (a non-PRESENT row) owns the entries src[j] .. + len[j] of
 // the uploaded Serials; they become the compact entries dst[j] ..: x = e << 32 |
@@ -115,12 +86,7 @@ __global__ __launch_bounds__(kNiThreads) void k_ni_rows(const uint64_t* __restri
 	}
 }
 
-// k_poll_part_walk's sibling.  One workgroup per element partition (<=
-// kRpGroupCap entries, keys h_residual << 32 | entry index from rp_group),
-// sorted in LDS so that each element's entries are one run in entry order --
-// arrival order, and inside an input the Serial's order.  One thread per run:
-// C0[e] (absent: below every prio), then each input's last entry of e; an
-// event wherever the prio exceeds the running maximum marks its row accepted
+// su_sort_walk over the acceptance entries: an event marks its row accepted
 // (every writer stores the same 1).  Read-only on corpusSignal (cs == nullptr:
 // a nil corpusSignal); the events are committed by k_ni_commit.
 __global__ __launch_bounds__(kNiThreads) void k_ni_walk(const uint64_t* __restrict__ keys,
@@ -131,54 +97,11 @@ __global__ __launch_bounds__(kNiThreads) void k_ni_walk(const uint64_t* __restri
                                                         unsigned long long* nev, uint8_t* accepted,
                                                         const unsigned long long* ctr)
 {
-	__shared__ uint64_t k[kRpGroupCap];
-	__shared__ uint64_t out[kRpGroupCap];
-	__shared__ uint32_t s_n;
-	__shared__ unsigned long long s_base;
-	if (ctr[kCntSpill])
-		return;  // a partition past kRpGroupCap: the batch takes the sequential path
-	const uint32_t p = blockIdx.x, tid = threadIdx.x, b0 = base[p], n = base[p + 1] - b0;
-	if (n == 0 || n > kRpGroupCap)
-		return;
-	const uint32_t N = ni_pow2(n);
-	for (uint32_t i = tid; i < N; i += kNiThreads)
-		k[i] = i < n ? keys[b0 + i] : kNiPad;
-	if (tid == 0)
-		s_n = 0;
-	ni_sort(k, N);
-	const uint32_t hp = pbits ? p << (32 - pbits) : 0;
-	for (uint32_t i = tid; i < n; i += kNiThreads) {
-		const uint32_t hr = (uint32_t)(k[i] >> 32);
-		if (i > 0 && (uint32_t)(k[i - 1] >> 32) == hr)
-			continue;  // not the head of e's run
-		const uint32_t e = fmix32_inv(hp | hr);
-		uint64_t v = 0;
-		int m = -1000;  // absent: below every prio (signal.go:79-81)
-		if (cs && tbl_lookup(cs, cs_bmask, e, v) >= 0 && slot_live(v))
-			m = slot_prio(v);
-		uint32_t row_next = 0;
-		for (uint32_t q = i; q < n && (uint32_t)(k[q] >> 32) == hr; q++) {
-			const uint32_t r = (uint32_t)k[q], row = q == i ? rec_row[r] : row_next;
-			const bool more = q + 1 < n && (uint32_t)(k[q + 1] >> 32) == hr;
-			row_next = more ? rec_row[(uint32_t)k[q + 1]] : 0;
-			if (more && row_next == row)
-				continue;  // an earlier duplicate inside one Serial
-			const int pr = rec_prio[r];
-			if (pr > m) {
-				out[atomicAdd(&s_n, 1u)] = ((uint64_t)e << 32) | prio_biased((int8_t)pr);
-				accepted[row] = 1;
-				m = pr;
-			}
-		}
-	}
-	__syncthreads();
-	const uint32_t ne = s_n;
-	if (tid == 0)
-		s_base = ne ? atomicAdd(nev, (unsigned long long)ne) : 0;
-	__syncthreads();
-	for (uint32_t i = tid; i < ne; i += kNiThreads)
-		if (s_base + i < ev_cap)  // (at most one event per entry: cannot fail)
-			ev[s_base + i] = out[i];
+	su_sort_walk(keys, base, pbits, rec_row, rec_prio, cs, cs_bmask, ev, ev_cap, nev, ctr,
+	             [&](uint32_t e, uint32_t row, int pr) {
+		             accepted[row] = 1;
+		             return ((uint64_t)e << 32) | prio_biased((int8_t)pr);
+	             });
 }
 
 // The commit, one launch: workgroups [0, ev_blocks) max-merge the events into
@@ -252,83 +175,6 @@ __global__ __launch_bounds__(kNiThreads) void k_ni_gather(NiRows R, const uint64
 	}
 }
 
-// tile b = keys [tile_idx[b] * kNiTile, + kNiTile) of group tile_g[b]
-struct NiTiles {
-	const uint64_t* g_base;
-	const uint32_t* g_len;
-	const uint32_t* tile_g;
-	const uint32_t* tile_idx;
-	uint64_t ntiles;
-};
-
-__global__ __launch_bounds__(kNiThreads) void k_ni_tile_sort(NiTiles T, const uint64_t* __restrict__ keys, uint64_t* buf)
-{
-	__shared__ uint64_t k[kNiTile];
-	const uint32_t tid = threadIdx.x;
-	for (uint64_t b = blockIdx.x; b < T.ntiles; b += gridDim.x) {
-		const uint32_t g = T.tile_g[b];
-		const uint64_t len = T.g_len[g], lo = (uint64_t)T.tile_idx[b] * kNiTile, gb = T.g_base[g] + lo;
-		const uint32_t n = (uint32_t)std::min<uint64_t>(len - lo, kNiTile), N = ni_pow2(n);
-		for (uint32_t i = tid; i < N; i += kNiThreads)
-			k[i] = i < n ? keys[gb + i] : kNiPad;
-		ni_sort(k, N);
-		for (uint32_t i = tid; i < n; i += kNiThreads)
-			buf[gb + i] = k[i];
-		__syncthreads();  // k is refilled for the next tile
-	}
-}
-
-// the first index in [lo, hi) of the sorted p whose key is >= x (kUpper: > x)
-template <bool kUpper>
-__device__ __forceinline__ uint64_t ni_bound(const uint64_t* __restrict__ p, uint64_t lo, uint64_t hi, uint64_t x)
-{
-	for (uint32_t it = 0; it < 33 && lo < hi; it++) {  // hi - lo < 2^32 halves every step
-		const uint64_t mid = lo + ((hi - lo) >> 1);
-		const uint64_t v = p[mid];
-		if (kUpper ? v <= x : v < x)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-// One merge pass: sorted runs of w keys -> sorted runs of 2 w keys, by rank
-// (cover.hip k_cover_merge).  A group of at most w keys is copied through, so
-// that every group is in the same buffer after every pass.
-__global__ __launch_bounds__(kNiThreads) void k_ni_merge(NiTiles T, uint64_t w, const uint64_t* __restrict__ src,
-                                                         uint64_t* dst)
-{
-	for (uint64_t b = blockIdx.x; b < T.ntiles; b += gridDim.x) {
-		const uint32_t g = T.tile_g[b];
-		const uint64_t len = T.g_len[g], lo = (uint64_t)T.tile_idx[b] * kNiTile;
-		const uint64_t n = std::min<uint64_t>(len - lo, kNiTile);
-		const uint64_t* s = src + T.g_base[g];
-		uint64_t* d = dst + T.g_base[g];
-		// a tile lies inside one run (w is a multiple of the tile): uniform per workgroup
-		const uint64_t pb = lo / (2 * w) * (2 * w), a1 = std::min(pb + w, len), b1 = std::min(pb + 2 * w, len);
-		const bool left = lo < a1;
-		for (uint64_t li = lo + threadIdx.x; li < lo + n; li += kNiThreads) {
-			const uint64_t x = s[li];
-			const uint64_t pos = left ? li + (ni_bound<false>(s, a1, b1, x) - a1)
-			                          : pb + (li - a1) + (ni_bound<true>(s, pb, a1, x) - pb);
-			d[pos] = x;
-		}
-	}
-}
-
-__device__ __forceinline__ uint32_t ni_wave_incl_scan(uint32_t v)
-{
-	const uint32_t lane = lane_id();
-#pragma unroll
-	for (uint32_t o = 1; o < 64; o <<= 1) {
-		const uint32_t x = __shfl_up(v, o, 64);
-		if (lane >= o)
-			v += x;
-	}
-	return v;
-}
-
 // One workgroup per group streams its sorted keys.  An element's entries are
 // one run in arrival order; the run's head thread walks it: per merge row the
 // last entry (Deserialize: a later duplicate wins, signal.go:59-71), the max
@@ -355,7 +201,7 @@ __global__ __launch_bounds__(kNiThreads) void k_ni_reduce(const uint64_t* __rest
 				e = (uint32_t)(s[i] >> 32);
 				head = i == 0 || (uint32_t)(s[i - 1] >> 32) != e;
 			}
-			const uint32_t incl = ni_wave_incl_scan((uint32_t)head);
+			const uint32_t incl = wave_incl_scan((uint32_t)head);
 			if (lane_id() == 63)
 				s_w[it][wv] = incl;
 			__syncthreads();  // (s_w[it] is rewritten two sweeps on, past the next sweep's barrier)
@@ -388,25 +234,6 @@ __global__ __launch_bounds__(kNiThreads) void k_ni_reduce(const uint64_t* __rest
 		__syncthreads();  // s_w starts over with the next group
 	}
 }
-
-// group g's cnt[g] results from its base to the CSR position off[g]
-__global__ __launch_bounds__(kNiThreads) void k_ni_csr(const uint32_t* __restrict__ st_e, const int8_t* __restrict__ st_p,
-                                                       const uint64_t* __restrict__ g_base,
-                                                       const uint64_t* __restrict__ off, uint32_t G, uint32_t* out_e,
-                                                       int8_t* out_p)
-{
-	for (uint32_t g = blockIdx.x; g < G; g += gridDim.x) {
-		const uint64_t a = off[g], n = off[g + 1] - a, gb = g_base[g];
-		for (uint64_t x = threadIdx.x; x < n; x += kNiThreads) {
-			out_e[a + x] = st_e[gb + x];
-			out_p[a + x] = st_p[gb + x];
-		}
-	}
-}
-
-static size_t ni_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static int ni_grid(uint64_t n) { return (int)std::min<uint64_t>(std::max<uint64_t>(n, 1), 1u << 16); }
 
 // host array -> scratch slot (the copy is stream-ordered; `h` outlives the call's last synchronisation)
 static int ni_upload(syzsig_ctx* ctx, int slot, const void* h, size_t bytes, void** d)
@@ -526,16 +353,16 @@ static int ni_accept_batched(syzsig_ctx* ctx, const NiBatch& B, const syzsig_set
 	void *dtab, *dx, *drec, *dev, *dacc;
 	SYZ_TRY(ni_upload(ctx, kWsNiStageA, tab.data(), (size_t)R * 24, &dtab));
 	SYZ_TRY(ws_get(ctx, kWsNiStageB, nA * 8 + 64, &dx));
-	SYZ_TRY(ws_get(ctx, kWsNiRecs, ni_align(nA * 4) + nA + 64, &drec));
+	SYZ_TRY(ws_get(ctx, kWsNiRecs, align256(nA * 4) + nA + 64, &drec));
 	SYZ_TRY(ws_get(ctx, kWsNiEvents, nA * 8 + 64, &dev));
 	SYZ_TRY(ws_get(ctx, kWsNiAccepted, (size_t)K + 64, &dacc));
 	uint32_t* rec_row = (uint32_t*)drec;
-	int8_t* rec_prio = (int8_t*)((char*)drec + ni_align(nA * 4));
+	int8_t* rec_prio = (int8_t*)((char*)drec + align256(nA * 4));
 	SYZ_HIP(hipMemsetAsync(dacc, 0, K, s));
 	unsigned long long* nev = &ctx->d_cnt[kCntAux];
 	if (nA) {
 		const uint64_t* t = (const uint64_t*)dtab;
-		k_ni_rows<<<ni_grid(R), kNiThreads, 0, s>>>(t, t + R, (const uint32_t*)(t + 2 * (size_t)R),
+		k_ni_rows<<<grid_cap(R, kNiMaxGrid), kNiThreads, 0, s>>>(t, t + R, (const uint32_t*)(t + 2 * (size_t)R),
 		                                            (const uint32_t*)(t + 2 * (size_t)R) + R, R, B.d_elems, B.d_prios,
 		                                            (uint64_t*)dx, rec_row, rec_prio);
 		uint64_t* keys;
@@ -647,30 +474,32 @@ static int ni_merge_keys(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, 
 	SYZ_TRY(ws_get(ctx, kWsNiBufA, nM * 8 + 64, &dba));
 	if (maxlen > kNiTile)
 		SYZ_TRY(ws_get(ctx, kWsNiBufB, nM * 8 + 64, &dbb));
-	SYZ_TRY(ws_get(ctx, kWsNiEntries, ni_align(nM * 4) + nM + 64, &dent));
-	SYZ_TRY(ws_get(ctx, kWsNiState, ni_align(nM * 4) + ni_align(nM) + ni_align((size_t)G * 4) + ((size_t)G + 1) * 8 + 64, &dst_));
+	SYZ_TRY(ws_get(ctx, kWsNiEntries, align256(nM * 4) + nM + 64, &dent));
+	SYZ_TRY(ws_get(ctx, kWsNiState, align256(nM * 4) + align256(nM) + align256((size_t)G * 4) + ((size_t)G + 1) * 8 + 64, &dst_));
 	SYZ_TRY(ws_get(ctx, kWsNiGroupCover, cM * 4 + 64, &dgcov));
 	const uint64_t* drt64 = (const uint64_t*)drt;
 	const uint32_t* drt32 = (const uint32_t*)(drt64 + 4 * (size_t)M);
 	const NiRows R{drt64, drt64 + M, drt64 + 2 * (size_t)M, drt64 + 3 * (size_t)M, drt32, drt32 + M, drt32 + 2 * (size_t)M, M};
 	const uint64_t* dg_base = (const uint64_t*)dgt;
 	const uint32_t* dg_len = (const uint32_t*)(dg_base + G);
-	const NiTiles T{dg_base, dg_len, (const uint32_t*)dtt, (const uint32_t*)dtt + ntiles, ntiles};
+	// every group is a "long segment" of the tile table, in place: group g's keys at g_base[g] of keys and buffers
+	const SuTiles T{nullptr, (uint64_t*)dgt, (uint32_t*)dg_len, (uint32_t*)dtt, (uint32_t*)dtt + ntiles, G, ntiles};
+	const SuSegs S{dkeys, 1, dg_base, dg_len, 1, dg_len, G};
 	uint32_t* ent_row = (uint32_t*)dent;
-	int8_t* ent_prio = (int8_t*)((char*)dent + ni_align(nM * 4));
+	int8_t* ent_prio = (int8_t*)((char*)dent + align256(nM * 4));
 	uint32_t* st_e = (uint32_t*)dst_;
-	int8_t* st_p = (int8_t*)((char*)dst_ + ni_align(nM * 4));
-	uint32_t* d_cnt_g = (uint32_t*)((char*)st_p + ni_align(nM));
-	uint64_t* d_off = (uint64_t*)((char*)d_cnt_g + ni_align((size_t)G * 4));
-	k_ni_gather<<<ni_grid(M), kNiThreads, 0, s>>>(R, dg_base, B.d_elems, B.d_prios, B.d_cover, (uint64_t*)dkeys, ent_row,
+	int8_t* st_p = (int8_t*)((char*)dst_ + align256(nM * 4));
+	uint32_t* d_cnt_g = (uint32_t*)((char*)st_p + align256(nM));
+	uint64_t* d_off = (uint64_t*)((char*)d_cnt_g + align256((size_t)G * 4));
+	k_ni_gather<<<grid_cap(M, kNiMaxGrid), kNiThreads, 0, s>>>(R, dg_base, B.d_elems, B.d_prios, B.d_cover, (uint64_t*)dkeys, ent_row,
 	                                              ent_prio, (uint32_t*)dgcov);
-	k_ni_tile_sort<<<ni_grid(ntiles), kNiThreads, 0, s>>>(T, (const uint64_t*)dkeys, (uint64_t*)dba);
+	k_su_tile_sort<NiTile><<<grid_cap(ntiles, kNiMaxGrid), kNiThreads, 0, s>>>(S, T, (uint64_t*)dba, nullptr);
 	uint64_t *src = (uint64_t*)dba, *dst = (uint64_t*)dbb, passes = 0;
 	for (uint64_t w = kNiTile; w < maxlen; w <<= 1, passes++) {
-		k_ni_merge<<<ni_grid(ntiles), kNiThreads, 0, s>>>(T, w, src, dst);
+		k_su_merge<NiTile::Key, kNiTile><<<grid_cap(ntiles, kNiMaxGrid), kNiThreads, 0, s>>>(T, w, src, dst, nullptr);
 		std::swap(src, dst);
 	}
-	k_ni_reduce<<<ni_grid(G), kNiThreads, 0, s>>>(src, dg_base, dg_len, G, ent_row, ent_prio, st_e, st_p, d_cnt_g);
+	k_ni_reduce<<<grid_cap(G, kNiMaxGrid), kNiThreads, 0, s>>>(src, dg_base, dg_len, G, ent_row, ent_prio, st_e, st_p, d_cnt_g);
 	SYZ_HIP(hipGetLastError());
 	std::vector<uint32_t> cnt(G);
 	SYZ_HIP(hipMemcpyAsync(cnt.data(), d_cnt_g, (size_t)G * 4, hipMemcpyDeviceToHost, s));
@@ -680,10 +509,11 @@ static int ni_merge_keys(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, 
 		off[g + 1] = off[g] + std::min<uint32_t>(cnt[g], g_len[g]);
 	const uint64_t total = off[G];
 	void* dout;
-	SYZ_TRY(ws_get(ctx, kWsNiOut, ni_align(total * 4) + total + 64, &dout));
-	int8_t* out_p = (int8_t*)((char*)dout + ni_align(total * 4));
+	SYZ_TRY(ws_get(ctx, kWsNiOut, align256(total * 4) + total + 64, &dout));
+	int8_t* out_p = (int8_t*)((char*)dout + align256(total * 4));
 	SYZ_HIP(hipMemcpyAsync(d_off, off.data(), ((size_t)G + 1) * 8, hipMemcpyHostToDevice, s));
-	k_ni_csr<<<ni_grid(G), kNiThreads, 0, s>>>(st_e, st_p, dg_base, d_off, G, (uint32_t*)dout, out_p);
+	k_su_gather<<<grid_cap(G, kNiMaxGrid), kNiThreads, 0, s>>>(st_e, dg_base, 1, 1, d_off, G, (uint32_t*)dout, nullptr);
+	k_su_gather<<<grid_cap(G, kNiMaxGrid), kNiThreads, 0, s>>>(st_p, dg_base, 1, 1, d_off, G, out_p, nullptr);
 	SYZ_HIP(hipGetLastError());
 	out->elems.resize(total);
 	out->prios.resize(total);
@@ -701,10 +531,10 @@ static int ni_merge_keys(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, 
 	// the covers: one item per group with one run, the group's gathered covers
 	// (cover.hip's segmented sort-unique; a run with signal, executed, no errno)
 	if (cM) {
-		const size_t o_keep = ni_align(G), o_exec = o_keep + ni_align(G), o_errno = o_exec + ni_align(G),
-		             o_roff = o_errno + ni_align((size_t)G * 4), o_cs = o_roff + ni_align(((size_t)G + 1) * 8),
-		             o_cl = o_cs + ni_align((size_t)G * 8), o_ooff = o_cl + ni_align((size_t)G * 4),
-		             o_end = o_ooff + ni_align(((size_t)G + 1) * 8);
+		const size_t o_keep = align256(G), o_exec = o_keep + align256(G), o_errno = o_exec + align256(G),
+		             o_roff = o_errno + align256((size_t)G * 4), o_cs = o_roff + align256(((size_t)G + 1) * 8),
+		             o_cl = o_cs + align256((size_t)G * 8), o_ooff = o_cl + align256((size_t)G * 4),
+		             o_end = o_ooff + align256(((size_t)G + 1) * 8);
 		std::vector<char> it(o_end, 0);
 		std::fill(it.begin() + o_keep, it.begin() + o_keep + G, 1);
 		std::fill(it.begin() + o_exec, it.begin() + o_exec + G, 1);
@@ -722,7 +552,7 @@ static int ni_merge_keys(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, 
 		                                (const uint8_t*)(dit + o_exec), (const uint32_t*)dgcov, cM,
 		                                (const uint64_t*)(dit + o_cs), (const uint32_t*)(dit + o_cl),
 		                                (uint64_t*)(dit + o_ooff), (uint32_t*)dcout, cM, &ctot));
-		ctx->ni_stats[3] = ctx->h_cnt[kCntAux];  // (cover.hip kCvLarge: the groups past its tile)
+		ctx->ni_stats[3] = ctx->h_cnt[kSuLarge];  // (the groups past cover.hip's tile)
 		std::vector<uint64_t> coff((size_t)G + 1);
 		SYZ_HIP(hipMemcpyAsync(coff.data(), dit + o_ooff, ((size_t)G + 1) * 8, hipMemcpyDeviceToHost, s));
 		out->cover.resize(ctot);
@@ -787,7 +617,7 @@ static int ni_commit(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, NiAc
 		co[i] = B.cover_off[i] - B.cover_off[0];
 	SYZ_TRY(ni_upload(ctx, kWsNiStageB, co.data(), ((size_t)B.K + 1) * 8, &dco));
 	SYZ_TRY(counters_reset(ctx));
-	const uint32_t eb = (uint32_t)grid_for(A->E, kNiThreads, 8192), rb = cacc ? (uint32_t)ni_grid(B.K) : 0;
+	const uint32_t eb = (uint32_t)grid_for(A->E, kNiThreads, 8192), rb = cacc ? (uint32_t)grid_cap(B.K, kNiMaxGrid) : 0;
 	k_ni_commit<<<eb + rb, kNiThreads, 0, s>>>(A->d_ev, A->E, eb, cs->slots, cs->nbuckets - 1, A->d_acc,
 	                                           (const uint8_t*)dfl, (const uint64_t*)dco, B.K, B.d_cover, cv->slots,
 	                                           cv->nbuckets - 1, ctx->d_cnt);

@@ -23,30 +23,15 @@
 // `completed` before any key is read (k_cover_prep_calls), as doexit(0)
 // happens inside the signal loop before any cover is written.
 //
-// Kernels (T = kCvTile keys, SYZSIG_COVER_TILE):
+// The segmented sort-unique is segsort.h's, over u32 keys with this file's
+// own tile routines (T = kCvTile keys, SYZSIG_COVER_TILE; 4 T bytes of LDS, 16
+// KB at T = 4096: several workgroups share a CU): 16-B global loads on a
+// source's aligned body (cv_load), the quad sort below (cv_sort), a quad per
+// thread in the unique sweep (cv_unique_write), and key ranges of whole quads
+// in the sort buffers, so that the tile stores and the sweep's loads are 16 B.
 //   k_cover_prep_calls / _items   validate; per segment its length (and per
 //                                 run of an item its merged length); count the
 //                                 segments longer than T, their tiles and keys
-//   k_cover_small     one workgroup per segment of <= T keys: the keys into
-//                     LDS (16-B global loads on the aligned body), padded to a
-//                     power of two with 0xffffffff, bitonic sort, then flag
-//                     differing neighbours, block scan, compacted write.
-//                     4 T bytes of LDS (16 KB at T = 4096): several
-//                     workgroups share a CU.
-//   segments longer than T go through workspace buffers in HBM:
-//   k_cover_register  each gets a slot, a key range and its tiles (three
-//                     atomics per SEGMENT; none per key anywhere)
-//   k_cover_tile_sort one workgroup per tile of T keys: sorted in LDS
-//   k_cover_merge     ceil(log2(tiles of the longest segment)) passes, known
-//                     at launch: runs of w keys merged pairwise into runs of
-//                     2 w by rank -- a key of the left run goes to its index
-//                     plus the keys of the right run below it (lower bound),
-//                     a key of the right run to its index plus the keys of the
-//                     left run not above it (upper bound): a bijection onto
-//                     the pair's range, duplicates included, no waiting
-//   k_cover_unique_large  one workgroup per segment streams its sorted keys:
-//                     flags, block scan with a running count, compacted write
-// Every loop is bounded by a segment length, a run count or the pass count.
 //
 // The LDS sort.  The compare-exchanges of strides 2 and 1 of every stage run
 // in registers on the thread's own 16-B quad (no barrier between them, and
@@ -57,7 +42,7 @@
 // bound by their register transfer, not by the array.
 #include <algorithm>
 
-#include "internal.h"
+#include "segsort.h"
 
 namespace syz {
 
@@ -65,52 +50,16 @@ namespace syz {
 #define SYZ_COVER_TILE SYZSIG_COVER_TILE
 #endif
 constexpr uint32_t kCvTile = SYZ_COVER_TILE;
-constexpr uint32_t kCvThreads = 256;
+constexpr uint32_t kCvThreads = kSuThreads;
 constexpr uint32_t kCvSweep = 4 * kCvThreads;   // keys per unique sweep: one quad per thread
+constexpr uint32_t kCvAlign = 4;                // a long segment's key range: whole quads, 16-B aligned
 constexpr uint32_t kCvMaxRuns = 8;
 constexpr uint32_t kCvMaxSeg = 0x7fffffffu;     // keys per segment (an item's concatenated runs)
-constexpr uint32_t kCvPad = 0xffffffffu;
 static_assert((kCvTile & (kCvTile - 1)) == 0 && kCvTile >= kCvSweep, "tile: a power of two, at least one sweep");
 static_assert(kCvTile * 4 <= 64 * 1024, "a workgroup's LDS stays at or below 64 KB");
 
-// the context's counters as this file uses them (zeroed per call)
-constexpr int kCvLarge = kCntAux, kCvTiles = kCntAux2, kCvKeys = kCntCandidates, kCvMaxLen = kCntTouched,
-              kCvTotal = kCntChanged, kCvCurLarge = kCntDefer, kCvCurTiles = kCntDeferNs, kCvCurKeys = kCntDistinct;
-
-// Segment s is the concatenation of its R sources: keys src[src_start[s * R + r]
-// .. + src_len[s * R + r]), seg_len[s] of them in all; its survivors go to
-// out[out_pos[s] ..], their count to out_cnt[s].
-struct CvSegs {
-	const void* src;  // u64 PCs (the low words are the keys) or u32 keys
-	const uint64_t* src_start;
-	const uint32_t* src_len;
-	uint32_t R;
-	const uint32_t* seg_len;
-	uint64_t nseg;
-	uint32_t* out;
-	const uint64_t* out_pos;
-	uint32_t* out_cnt;
-};
-
-// the segments longer than a tile, their key ranges in the sort buffers and
-// the tiles of all of them
-struct CvLarge {
-	const uint64_t* lg_seg;
-	const uint64_t* lg_base;   // multiple of 4 keys: 16-B aligned
-	const uint32_t* tile_lg;
-	const uint32_t* tile_idx;
-};
-
-__device__ __forceinline__ void cv_count_large(uint32_t len, uint64_t& nl, uint64_t& nt, uint64_t& nk,
-                                               unsigned long long* cnt)
-{
-	if (len > kCvTile) {
-		nl++;
-		nt += (len + kCvTile - 1) / kCvTile;
-		nk += ((uint64_t)len + 3) & ~3ull;
-		atomicMax(&cnt[kCvMaxLen], (unsigned long long)len);
-	}
-}
+// survivors: u32 keys (SuSegs::src: u64 PCs, whose low words are the keys, or u32 keys)
+using CvOut = SuOutKeys<SuU32>;
 
 // executor.h:514-527 per call: seg_len[c] = call_len[c] for a call with a
 // cover record (c - prog_call[p] < completed[p]), else 0.  Validates every
@@ -138,13 +87,13 @@ __global__ __launch_bounds__(64) void k_cover_prep_calls(const uint64_t* __restr
 			}
 			const uint32_t eff = c - cb < done ? len : 0;
 			seg_len[c] = eff;
-			cv_count_large(eff, nl, nt, nk, cnt);
+			su_count_large<kCvTile, kCvAlign>(eff, nl, nt, nk, cnt);
 		}
 	}
 	block_count(&cnt[kCntError], err);
-	block_count(&cnt[kCvLarge], nl);
-	block_count(&cnt[kCvTiles], nt);
-	block_count(&cnt[kCvKeys], nk);
+	block_count(&cnt[kSuLarge], nl);
+	block_count(&cnt[kSuTiles], nt);
+	block_count(&cnt[kSuKeys], nk);
 }
 
 // proc.go:119-139 per item: run r of a kept item is merged (:139) unless the
@@ -179,61 +128,20 @@ __global__ __launch_bounds__(256) void k_cover_prep_items(
 		}
 		seg_len[i] = (uint32_t)total;
 		tot = total;
-		cv_count_large((uint32_t)total, nl, nt, nk, cnt);
+		su_count_large<kCvTile, kCvAlign>((uint32_t)total, nl, nt, nk, cnt);
 	}
 	block_count(&cnt[kCntError], err);
 	block_count(&cnt[kCntOverflow], ovf);
-	block_count(&cnt[kCvLarge], nl);
-	block_count(&cnt[kCvTiles], nt);
-	block_count(&cnt[kCvKeys], nk);
-	block_count(&cnt[kCvTotal], tot);
-}
-
-template <typename T>
-__device__ __forceinline__ T cv_wave_incl_scan(T v)
-{
-	const uint32_t lane = lane_id();
-#pragma unroll
-	for (uint32_t o = 1; o < 64; o <<= 1) {
-		const T x = __shfl_up(v, o, 64);
-		if (lane >= o)
-			v += x;
-	}
-	return v;
-}
-
-// off[0..n] = the exclusive prefix sums of v[0..n) (one workgroup)
-__global__ __launch_bounds__(kCvThreads) void k_cover_scan(const uint32_t* __restrict__ v, uint64_t n, uint64_t* off)
-{
-	__shared__ uint64_t s_w[kCvThreads / 64];
-	const uint32_t w = threadIdx.x >> 6;
-	uint64_t run = 0;
-	for (uint64_t base = 0; base < n; base += kCvThreads) {
-		const uint64_t i = base + threadIdx.x;
-		const uint64_t x = i < n ? v[i] : 0;  // (64-bit sums: 256 lengths below 2^31 may pass 2^32)
-		const uint64_t incl = cv_wave_incl_scan(x);
-		if (lane_id() == 63)
-			s_w[w] = incl;
-		__syncthreads();
-		uint64_t wb = 0, tot = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < kCvThreads / 64; k++) {
-			wb += k < w ? s_w[k] : 0;
-			tot += s_w[k];
-		}
-		if (i < n)
-			off[i] = run + wb + incl - x;
-		run += tot;
-		__syncthreads();
-	}
-	if (threadIdx.x == 0)
-		off[n] = run;
+	block_count(&cnt[kSuLarge], nl);
+	block_count(&cnt[kSuTiles], nt);
+	block_count(&cnt[kSuKeys], nk);
+	block_count(&cnt[kSuTotal], tot);
 }
 
 // k[0 .. n) = the keys [lo, lo + n) of segment `seg` (workgroup-wide).  A
 // source's 16-B aligned body is read 16 B per lane, its ragged ends by a few lanes.
 template <bool k64>
-__device__ __forceinline__ void cv_load(const CvSegs& S, uint64_t seg, uint32_t lo, uint32_t n, uint32_t* k)
+__device__ __forceinline__ void cv_load(const SuSegs& S, uint64_t seg, uint32_t lo, uint32_t n, uint32_t* k)
 {
 	const uint32_t tid = threadIdx.x;
 	uint64_t o = 0;
@@ -359,7 +267,7 @@ __device__ __forceinline__ uint32_t cv_unique_write(uint32_t n, uint32_t* out, Q
 		const bool f0 = i0 < n && (i0 == 0 || v.x != pv), f1 = i0 + 1 < n && v.y != v.x,
 		           f2 = i0 + 2 < n && v.z != v.y, f3 = i0 + 3 < n && v.w != v.z;
 		const uint32_t c = (uint32_t)f0 + f1 + f2 + f3;
-		const uint32_t incl = cv_wave_incl_scan(c);
+		const uint32_t incl = wave_incl_scan(c);
 		if (lane_id() == 63)
 			s_w[it][w] = incl;
 		__syncthreads();  // (s_w[it] is rewritten two sweeps on, past the next sweep's barrier)
@@ -383,230 +291,59 @@ __device__ __forceinline__ uint32_t cv_unique_write(uint32_t n, uint32_t* out, Q
 	return run;
 }
 
-__device__ __forceinline__ uint32_t cv_pow2(uint32_t n)
-{
-	uint32_t N = 4;
-	while (N < n)
-		N <<= 1;
-	return N;
-}
-
+// segsort.h's tile type over the routines above (k64: the source holds u64 PCs)
 template <bool k64>
-__global__ __launch_bounds__(kCvThreads) void k_cover_small(CvSegs S)
-{
-	__shared__ __align__(16) uint32_t k[kCvTile];
-	const uint32_t tid = threadIdx.x;
-	for (uint64_t seg = blockIdx.x; seg < S.nseg; seg += gridDim.x) {
-		const uint32_t n = S.seg_len[seg];
-		if (n > kCvTile)
-			continue;  // k_cover_unique_large writes its count
-		if (n == 0) {
-			if (tid == 0)
-				S.out_cnt[seg] = 0;
-			continue;
-		}
-		const uint32_t N = cv_pow2(n);  // <= kCvTile
-		cv_load<k64>(S, seg, 0, n, k);
-		for (uint32_t i = n + tid; i < N; i += kCvThreads)
-			k[i] = kCvPad;  // (>= every key: the first n sorted keys are the segment's)
-		__syncthreads();
-		cv_sort(k, N);
-		const uint32_t c = cv_unique_write(
-			n, S.out + S.out_pos[seg], [&](uint32_t i0) { return reinterpret_cast<const uint4*>(k)[i0 >> 2]; },
-			[&](uint32_t i0) { return k[i0 - 1]; });
-		if (tid == 0)
-			S.out_cnt[seg] = c;
-		__syncthreads();  // k is refilled for the next segment
+struct CvTile {
+	using Key = SuU32;
+	static constexpr uint32_t kTile = kCvTile, kAlign = kCvAlign, kMinPad = 4;
+	struct Lds {
+		__align__(16) uint32_t k[kCvTile];
+	};
+	static __device__ __forceinline__ void load(const SuSegs& S, uint64_t seg, uint32_t lo, uint32_t n, Lds& t)
+	{
+		cv_load<k64>(S, seg, lo, n, t.k);
 	}
-}
+	static __device__ __forceinline__ void sort(Lds& t, uint32_t n, uint32_t N)
+	{
+		for (uint32_t i = n + threadIdx.x; i < N; i += kCvThreads)
+			t.k[i] = SuU32::pad();  // (>= every key: the first n sorted keys are the segment's)
+		__syncthreads();
+		cv_sort(t.k, N);
+	}
+	// o 16-B aligned: a key range and a tile's offset in it are multiples of 4 keys
+	static __device__ __forceinline__ void store(const Lds& t, uint32_t n, uint32_t* o)
+	{
+		const uint32_t tid = threadIdx.x;
+		for (uint32_t q = tid; q < n >> 2; q += kCvThreads)
+			reinterpret_cast<uint4*>(o)[q] = reinterpret_cast<const uint4*>(t.k)[q];
+		if (tid < (n & 3))
+			o[(n & ~3u) + tid] = t.k[(n & ~3u) + tid];
+	}
+	// s 16-B aligned and readable in whole quads: a key range of the sort buffers, or the LDS tile
+	static __device__ __forceinline__ uint64_t unique_buf(uint32_t n, uint64_t seg, const CvOut& pol, const uint32_t* s)
+	{
+		return cv_unique_write(
+			n, pol.dst(seg), [&](uint32_t i0) { return reinterpret_cast<const uint4*>(s)[i0 >> 2]; },
+			[&](uint32_t i0) { return s[i0 - 1]; });
+	}
+	static __device__ __forceinline__ uint64_t unique_lds(uint32_t n, uint64_t seg, const CvOut& pol, const Lds& t)
+	{
+		return unique_buf(n, seg, pol, t.k);
+	}
+};
 
 // executor.h:525-527 without flag_dedup_cover: the PCs truncated, in trace order
-__global__ __launch_bounds__(kCvThreads) void k_cover_trunc(const uint64_t* __restrict__ pcs, CvSegs S)
+__global__ __launch_bounds__(kCvThreads) void k_cover_trunc(const uint64_t* __restrict__ pcs, SuSegs S, CvOut pol)
 {
 	for (uint64_t seg = blockIdx.x; seg < S.nseg; seg += gridDim.x) {
 		const uint32_t n = S.seg_len[seg];
 		const uint64_t g = S.src_start[seg];
-		uint32_t* o = S.out + S.out_pos[seg];
+		uint32_t* o = pol.dst(seg);
 		for (uint32_t i = threadIdx.x; i < n; i += kCvThreads)
 			o[i] = (uint32_t)pcs[g + i];
 		if (threadIdx.x == 0)
-			S.out_cnt[seg] = n;
+			pol.finish(seg, n);
 	}
-}
-
-// Every segment longer than a tile takes a slot, a key range (16-B aligned)
-// and its tiles.  The capacities are the counts k_cover_prep_* took over the
-// same lengths, so the checks cannot fail; they keep a write inside its array
-// whatever happens.
-__global__ __launch_bounds__(256) void k_cover_register(const uint32_t* __restrict__ seg_len, uint64_t nseg,
-                                                        uint64_t cap_large, uint64_t cap_tiles, uint64_t cap_keys,
-                                                        uint64_t* lg_seg, uint64_t* lg_base, uint32_t* tile_lg,
-                                                        uint32_t* tile_idx, unsigned long long* cnt)
-{
-	const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (s >= nseg)
-		return;
-	const uint32_t len = seg_len[s];
-	if (len <= kCvTile)
-		return;
-	const uint32_t nt = (len + kCvTile - 1) / kCvTile;
-	const uint64_t L = atomicAdd(&cnt[kCvCurLarge], 1ull), tb = atomicAdd(&cnt[kCvCurTiles], (unsigned long long)nt),
-	               kb = atomicAdd(&cnt[kCvCurKeys], (unsigned long long)(((uint64_t)len + 3) & ~3ull));
-	if (L >= cap_large || tb + nt > cap_tiles || kb + len > cap_keys) {
-		atomicAdd(&cnt[kCntError], 1ull);
-		return;
-	}
-	lg_seg[L] = s;
-	lg_base[L] = kb;
-	for (uint32_t t = 0; t < nt; t++) {
-		tile_lg[tb + t] = (uint32_t)L;
-		tile_idx[tb + t] = t;
-	}
-}
-
-template <bool k64>
-__global__ __launch_bounds__(kCvThreads) void k_cover_tile_sort(CvSegs S, CvLarge G, uint64_t ntiles, uint32_t* buf,
-                                                                const unsigned long long* cnt)
-{
-	__shared__ __align__(16) uint32_t k[kCvTile];
-	const uint32_t tid = threadIdx.x;
-	if (cnt[kCntError])
-		return;  // k_cover_register left a table unwritten: the call fails, nothing reads it
-	for (uint64_t b = blockIdx.x; b < ntiles; b += gridDim.x) {
-		const uint32_t L = G.tile_lg[b];
-		const uint64_t seg = G.lg_seg[L];
-		const uint32_t len = S.seg_len[seg], lo = G.tile_idx[b] * kCvTile;
-		const uint32_t n = len - lo < kCvTile ? len - lo : kCvTile, N = cv_pow2(n);
-		cv_load<k64>(S, seg, lo, n, k);
-		for (uint32_t i = n + tid; i < N; i += kCvThreads)
-			k[i] = kCvPad;
-		__syncthreads();
-		cv_sort(k, N);
-		uint32_t* o = buf + G.lg_base[L] + lo;  // 16-B aligned: base and lo are multiples of 4 keys
-		for (uint32_t q = tid; q < n >> 2; q += kCvThreads)
-			reinterpret_cast<uint4*>(o)[q] = reinterpret_cast<const uint4*>(k)[q];
-		if (tid < (n & 3))
-			o[(n & ~3u) + tid] = k[(n & ~3u) + tid];
-		__syncthreads();
-	}
-}
-
-// the first index in [lo, hi) of the sorted p whose key is >= x (kUpper: > x)
-template <bool kUpper>
-__device__ __forceinline__ uint64_t cv_bound(const uint32_t* __restrict__ p, uint64_t lo, uint64_t hi, uint32_t x)
-{
-	for (uint32_t it = 0; it < 32 && lo < hi; it++) {  // hi - lo < 2^31 halves every step
-		const uint64_t mid = lo + ((hi - lo) >> 1);
-		const uint32_t v = p[mid];
-		if (kUpper ? v <= x : v < x)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-// one merge pass: sorted runs of w keys -> sorted runs of 2 w keys
-__global__ __launch_bounds__(kCvThreads) void k_cover_merge(const uint32_t* __restrict__ seg_len, CvLarge G,
-                                                            uint64_t ntiles, uint64_t w,
-                                                            const uint32_t* __restrict__ src, uint32_t* dst,
-                                                            const unsigned long long* cnt)
-{
-	if (cnt[kCntError])
-		return;
-	for (uint64_t b = blockIdx.x; b < ntiles; b += gridDim.x) {
-		const uint32_t L = G.tile_lg[b];
-		const uint64_t len = seg_len[G.lg_seg[L]], lo = (uint64_t)G.tile_idx[b] * kCvTile;
-		const uint64_t n = len - lo < kCvTile ? len - lo : kCvTile;
-		const uint32_t* s = src + G.lg_base[L];
-		uint32_t* d = dst + G.lg_base[L];
-		// a tile lies inside one run (w is a multiple of the tile): uniform per workgroup
-		const uint64_t pb = lo / (2 * w) * (2 * w), a1 = std::min(pb + w, len), b1 = std::min(pb + 2 * w, len);
-		const bool left = lo < a1;
-		for (uint64_t li = lo + threadIdx.x; li < lo + n; li += kCvThreads) {
-			const uint32_t x = s[li];
-			const uint64_t pos = left ? li + (cv_bound<false>(s, a1, b1, x) - a1)
-			                          : pb + (li - a1) + (cv_bound<true>(s, pb, a1, x) - pb);
-			d[pos] = x;
-		}
-	}
-}
-
-__global__ __launch_bounds__(kCvThreads) void k_cover_unique_large(CvSegs S, CvLarge G, uint64_t nlarge,
-                                                                   const uint32_t* __restrict__ buf,
-                                                                   const unsigned long long* cnt)
-{
-	if (cnt[kCntError])
-		return;
-	for (uint64_t L = blockIdx.x; L < nlarge; L += gridDim.x) {
-		const uint64_t seg = G.lg_seg[L];
-		const uint32_t n = S.seg_len[seg];
-		const uint32_t* s = buf + G.lg_base[L];  // 16-B aligned, padded to whole quads
-		const uint32_t c = cv_unique_write(
-			n, S.out + S.out_pos[seg], [&](uint32_t i0) { return reinterpret_cast<const uint4*>(s)[i0 >> 2]; },
-			[&](uint32_t i0) { return s[i0 - 1]; });
-		if (threadIdx.x == 0)
-			S.out_cnt[seg] = c;
-		__syncthreads();
-	}
-}
-
-// item i's sorted cover from the staging buffer to its place in the output
-__global__ __launch_bounds__(kCvThreads) void k_cover_gather(const uint32_t* __restrict__ stage,
-                                                             const uint64_t* __restrict__ stage_off,
-                                                             const uint64_t* __restrict__ off, uint64_t nitems,
-                                                             uint32_t* out, uint64_t* out_off)
-{
-	for (uint64_t i = blockIdx.x; i < nitems; i += gridDim.x) {
-		const uint64_t a = off[i], n = off[i + 1] - a;
-		const uint32_t* s = stage + stage_off[i];
-		for (uint64_t x = threadIdx.x; x < n; x += kCvThreads)
-			out[a + x] = s[x];
-		if (threadIdx.x == 0)
-			out_off[i] = a;
-	}
-	if (blockIdx.x == 0 && threadIdx.x == 0)
-		out_off[nitems] = off[nitems];
-}
-
-static size_t cv_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static int cv_grid(uint64_t n) { return (int)std::min<uint64_t>(std::max<uint64_t>(n, 1), 1u << 20); }
-
-// The sort-unique of every segment of S (lengths and counts as the prep
-// kernel left them in ctx->h_cnt).  Enqueues only.
-template <bool k64>
-static int cv_sort_unique(syzsig_ctx* ctx, const CvSegs& S)
-{
-	const hipStream_t s = ctx->stream;
-	const uint64_t nlarge = ctx->h_cnt[kCvLarge], ntiles = ctx->h_cnt[kCvTiles], nkeys = ctx->h_cnt[kCvKeys],
-	               maxlen = ctx->h_cnt[kCvMaxLen];
-	k_cover_small<k64><<<cv_grid(S.nseg), kCvThreads, 0, s>>>(S);
-	if (nlarge) {
-		char* tab;
-		void *ba, *bb;
-		const size_t o_base = cv_align(nlarge * 8), o_tlg = o_base + cv_align(nlarge * 8),
-		             o_tix = o_tlg + cv_align(ntiles * 4);
-		SYZ_TRY(ws_get(ctx, kWsSuTab, o_tix + cv_align(ntiles * 4), (void**)&tab));
-		SYZ_TRY(ws_get(ctx, kWsSuBufA, nkeys * 4 + 256, &ba));
-		SYZ_TRY(ws_get(ctx, kWsSuBufB, nkeys * 4 + 256, &bb));
-		uint64_t* lg_seg = (uint64_t*)tab;
-		uint64_t* lg_base = (uint64_t*)(tab + o_base);
-		uint32_t* tile_lg = (uint32_t*)(tab + o_tlg);
-		uint32_t* tile_idx = (uint32_t*)(tab + o_tix);
-		k_cover_register<<<(int)((S.nseg + 255) / 256), 256, 0, s>>>(S.seg_len, S.nseg, nlarge, ntiles, nkeys, lg_seg,
-		                                                             lg_base, tile_lg, tile_idx, ctx->d_cnt);
-		const CvLarge G{lg_seg, lg_base, tile_lg, tile_idx};
-		uint32_t *src = (uint32_t*)ba, *dst = (uint32_t*)bb;
-		k_cover_tile_sort<k64><<<cv_grid(ntiles), kCvThreads, 0, s>>>(S, G, ntiles, src, ctx->d_cnt);
-		for (uint64_t w = kCvTile; w < maxlen; w <<= 1) {
-			k_cover_merge<<<cv_grid(ntiles), kCvThreads, 0, s>>>(S.seg_len, G, ntiles, w, src, dst, ctx->d_cnt);
-			std::swap(src, dst);
-		}
-		k_cover_unique_large<<<cv_grid(nlarge), kCvThreads, 0, s>>>(S, G, nlarge, src, ctx->d_cnt);
-	}
-	SYZ_HIP(hipGetLastError());
-	return SYZSIG_OK;
 }
 
 }  // namespace syz
@@ -630,34 +367,27 @@ extern "C" int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uin
 	void* seg_len;
 	SYZ_TRY(ws_get(ctx, kWsSuMeta, ncalls * 4 + 256, &seg_len));
 	SYZ_TRY(counters_reset(ctx));
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
+	SYZ_TRY(su_time_begin(ctx));
 	// a call outside every program has no record
 	SYZ_HIP(hipMemsetAsync(seg_len, 0, ncalls * 4, s));
 	if (nprog)
-		k_cover_prep_calls<<<cv_grid(nprog), 64, 0, s>>>(d_call_start, d_call_len, ncalls, npc, d_prog_call, nprog,
+		k_cover_prep_calls<<<grid_cap(nprog), 64, 0, s>>>(d_call_start, d_call_len, ncalls, npc, d_prog_call, nprog,
 		                                                  d_completed, (uint32_t*)seg_len, ctx->d_cnt);
 	SYZ_HIP(hipGetLastError());
 	SYZ_TRY(counters_fetch(ctx));
 	if (ctx->h_cnt[kCntError])
 		return fail(SYZSIG_EINVAL, "edge_cover: malformed program/call ranges, completed past a program's calls, or "
 		                           "a call with >= 262144 PCs");
-	const CvSegs S{d_pcs, d_call_start, (const uint32_t*)seg_len, 1, (const uint32_t*)seg_len, ncalls,
-	               d_cover, d_call_start, d_cover_cnt};
+	const SuSegs S{d_pcs, 1, d_call_start, (const uint32_t*)seg_len, 1, (const uint32_t*)seg_len, ncalls};
+	const CvOut pol{d_cover, d_call_start, 1, d_cover_cnt};
 	if (flags & SYZSIG_COVER_DEDUP) {
-		SYZ_TRY(cv_sort_unique<true>(ctx, S));
+		SYZ_TRY((su_sort_unique<CvTile<true>, CvOut>(ctx, S, pol)));
 	} else {
-		k_cover_trunc<<<cv_grid(ncalls), kCvThreads, 0, s>>>(d_pcs, S);
+		k_cover_trunc<<<grid_cap(ncalls), kCvThreads, 0, s>>>(d_pcs, S, pol);
 		SYZ_HIP(hipGetLastError());
 	}
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
+	SYZ_TRY(su_time_end(ctx));
 	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->timing) {
-		float t = 0;
-		SYZ_HIP(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-		ctx->last_ms = t;
-	}
 	if (ctx->h_cnt[kCntError])
 		return fail(SYZSIG_EIO, "edge_cover: internal: a long segment did not fit its workspace");
 	return SYZSIG_OK;
@@ -688,18 +418,17 @@ extern "C" int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_
 	const uint64_t nruns = nitems * runs;
 	// src_len[nruns], seg_len[nitems], cnt[nitems], stage_off[nitems + 1], off[nitems + 1]
 	char* d;
-	const size_t o_seg = cv_align(nruns * 4), o_cnt = o_seg + cv_align(nitems * 4), o_soff = o_cnt + cv_align(nitems * 4),
-	             o_off = o_soff + cv_align((nitems + 1) * 8);
-	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_off + cv_align((nitems + 1) * 8), (void**)&d));
+	const size_t o_seg = align256(nruns * 4), o_cnt = o_seg + align256(nitems * 4), o_soff = o_cnt + align256(nitems * 4),
+	             o_off = o_soff + align256((nitems + 1) * 8);
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_off + align256((nitems + 1) * 8), (void**)&d));
 	uint32_t *src_len = (uint32_t*)d, *seg_len = (uint32_t*)(d + o_seg), *cnt = (uint32_t*)(d + o_cnt);
 	uint64_t *stage_off = (uint64_t*)(d + o_soff), *off = (uint64_t*)(d + o_off);
 	SYZ_TRY(counters_reset(ctx));
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
+	SYZ_TRY(su_time_begin(ctx));
 	k_cover_prep_items<<<(int)((nitems + 255) / 256), 256, 0, s>>>(nitems, runs, d_item_flags, d_item_keep, d_run_off,
 	                                                               d_run_errno, d_run_exec, ncover, d_run_cover_start,
 	                                                               d_run_cover_len, src_len, seg_len, ctx->d_cnt);
-	k_cover_scan<<<1, kCvThreads, 0, s>>>(seg_len, nitems, stage_off);
+	k_su_scan<<<1, kCvThreads, 0, s>>>(seg_len, nitems, stage_off);
 	SYZ_HIP(hipGetLastError());
 	SYZ_TRY(counters_fetch(ctx));
 	if (ctx->h_cnt[kCntError])
@@ -707,10 +436,11 @@ extern "C" int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_
 	if (ctx->h_cnt[kCntOverflow])
 		return fail(SYZSIG_ERANGE, "triage_cover: an item's runs hold 2^31 or more PCs");
 	void* stage;
-	SYZ_TRY(ws_get(ctx, kWsSuStage, ctx->h_cnt[kCvTotal] * 4 + 256, &stage));
-	const CvSegs S{d_cover, d_run_cover_start, src_len, runs, seg_len, nitems, (uint32_t*)stage, stage_off, cnt};
-	SYZ_TRY(cv_sort_unique<false>(ctx, S));
-	k_cover_scan<<<1, kCvThreads, 0, s>>>(cnt, nitems, off);
+	SYZ_TRY(ws_get(ctx, kWsSuStage, ctx->h_cnt[kSuTotal] * 4 + 256, &stage));
+	const SuSegs S{d_cover, 1, d_run_cover_start, src_len, runs, seg_len, nitems};
+	const CvOut pol{(uint32_t*)stage, stage_off, 1, cnt};
+	SYZ_TRY((su_sort_unique<CvTile<false>, CvOut>(ctx, S, pol)));
+	k_su_scan<<<1, kCvThreads, 0, s>>>(cnt, nitems, off);
 	SYZ_HIP(hipGetLastError());
 	uint64_t total = 0;
 	SYZ_HIP(hipMemcpyAsync(&total, off + nitems, 8, hipMemcpyDeviceToHost, s));
@@ -720,16 +450,10 @@ extern "C" int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_
 	*n_out = total;
 	if (total > cap)
 		return fail(SYZSIG_ERANGE, "triage_cover: the items' cover needs more than the given capacity");
-	k_cover_gather<<<cv_grid(nitems), kCvThreads, 0, s>>>((const uint32_t*)stage, stage_off, off, nitems, d_item_cover,
-	                                                     d_item_cover_off);
+	k_su_gather<<<grid_cap(nitems), kCvThreads, 0, s>>>((const uint32_t*)stage, stage_off, 1, 1, off, nitems, d_item_cover,
+	                                                    d_item_cover_off);
 	SYZ_HIP(hipGetLastError());
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
+	SYZ_TRY(su_time_end(ctx));
 	SYZ_HIP(hipStreamSynchronize(s));
-	if (ctx->timing) {
-		float t = 0;
-		SYZ_HIP(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-		ctx->last_ms = t;
-	}
 	return SYZSIG_OK;
 }

@@ -18,9 +18,10 @@
 // (e, p) routed to it:
 //   k_poll_x / rp_group        the entries grouped by element through the LDS
 //                              partitions of recs.hip (no device-wide sort)
-//   k_poll_part_walk           one workgroup per partition: its entries sorted
-//                              by (element, entry index) in LDS (bitonic), then
-//                              one thread per element: the events (read-only)
+//   k_poll_part_walk           segsort.h's su_sort_walk: one workgroup per
+//                              partition sorts its entries by (element, entry
+//                              index) in LDS, then one thread per element: the
+//                              events (read-only)
 //   k_poll_commit              maxSignal.Merge of the events, once every target exists
 //   k_poll_fanout              (target, e, p) of every event for every other
 //                              fuzzer into one max-table keyed by (target, e)
@@ -31,7 +32,7 @@
 
 #include <chrono>
 
-#include "internal.h"
+#include "segsort.h"
 
 namespace syz {
 
@@ -94,86 +95,20 @@ __global__ void k_poll_x(const uint32_t* __restrict__ elems, uint64_t n, uint64_
 		x[r] = ((uint64_t)elems[r] << 32) | r;
 }
 
-// One workgroup per element partition (<= kRpGroupCap entries, keys
-// h_residual << 32 | entry index from rp_group).  The keys are sorted in LDS
-// (bitonic, padded to a power of two), so each element's entries are one run
-// in entry order -- poll order, and inside a poll the Serial's order -- and
-// one thread per run walks it: M0[e], then each poll's last entry of e
-// (Deserialize: a later duplicate wins), an event wherever the prio exceeds
-// the running maximum.  Read-only on maxSignal: the events are committed by
-// k_poll_commit once every target set exists, so a failed allocation leaves
-// the manager untouched.  The block's events are gathered in LDS and written
-// with one device atomic.
-constexpr uint32_t kPollWalkThreads = 256;
-__global__ __launch_bounds__(kPollWalkThreads) void k_poll_part_walk(const uint64_t* __restrict__ keys,
-                                                                     const uint32_t* __restrict__ base, uint32_t pbits,
-                                                                     const uint32_t* __restrict__ rec_poll,
-                                                                     const int8_t* __restrict__ prios, const uint64_t* ms,
-                                                                     uint64_t ms_bmask, uint64_t* ev,
-                                                                     unsigned long long* nev,
-                                                                     const unsigned long long* ctr)
+// su_sort_walk over the polled entries; an event carries its poll.  Read-only
+// on maxSignal: the events are committed by k_poll_commit once every target
+// set exists, so a failed allocation leaves the manager untouched.
+__global__ __launch_bounds__(kSuThreads) void k_poll_part_walk(const uint64_t* __restrict__ keys,
+                                                               const uint32_t* __restrict__ base, uint32_t pbits,
+                                                               const uint32_t* __restrict__ rec_poll,
+                                                               const int8_t* __restrict__ prios, const uint64_t* ms,
+                                                               uint64_t ms_bmask, uint64_t* ev, uint64_t ev_cap,
+                                                               unsigned long long* nev, const unsigned long long* ctr)
 {
-	__shared__ uint64_t k[kRpGroupCap];
-	__shared__ uint64_t out[kRpGroupCap];
-	__shared__ uint32_t s_n;
-	__shared__ unsigned long long s_base;
-	if (ctr[kCntSpill])
-		return;  // a partition past kRpGroupCap: the batch takes the sequential path
-	const uint32_t p = blockIdx.x, tid = threadIdx.x, b0 = base[p], n = base[p + 1] - b0;
-	if (n == 0)
-		return;
-	uint32_t N = 2;
-	while (N < n)
-		N <<= 1;
-	for (uint32_t i = tid; i < N; i += kPollWalkThreads)
-		k[i] = i < n ? keys[b0 + i] : ~0ull;
-	if (tid == 0)
-		s_n = 0;
-	for (uint32_t size = 2; size <= N; size <<= 1) {
-		for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-			__syncthreads();
-			for (uint32_t t = tid; t < N / 2; t += kPollWalkThreads) {
-				const uint32_t i = 2 * t - (t & (stride - 1)), j = i + stride;
-				const uint64_t a = k[i], b = k[j];
-				if ((a > b) == ((i & size) == 0)) {
-					k[i] = b;
-					k[j] = a;
-				}
-			}
-		}
-	}
-	__syncthreads();
-	const uint32_t hp = p << (32 - pbits);
-	for (uint32_t i = tid; i < n; i += kPollWalkThreads) {
-		const uint32_t hr = (uint32_t)(k[i] >> 32);
-		if (i > 0 && (uint32_t)(k[i - 1] >> 32) == hr)
-			continue;  // not the head of e's run
-		const uint32_t e = fmix32_inv(hp | hr);
-		uint64_t v = 0;
-		int m = -1000;  // absent: below every prio (signal.go:79-81)
-		if (tbl_lookup(ms, ms_bmask, e, v) >= 0 && slot_live(v))
-			m = slot_prio(v);
-		uint32_t poll_next = 0;
-		for (uint32_t q = i; q < n && (uint32_t)(k[q] >> 32) == hr; q++) {
-			const uint32_t r = (uint32_t)k[q], poll = q == i ? rec_poll[r] : poll_next;
-			const bool more = q + 1 < n && (uint32_t)(k[q + 1] >> 32) == hr;
-			poll_next = more ? rec_poll[(uint32_t)k[q + 1]] : 0;
-			if (more && poll_next == poll)
-				continue;  // an earlier duplicate inside one Serial
-			const int pr = prios[r];
-			if (pr > m) {
-				out[atomicAdd(&s_n, 1u)] = ((uint64_t)e << 32) | ((uint64_t)(poll & 0xFFFFFFu) << 8) | prio_biased((int8_t)pr);
-				m = pr;
-			}
-		}
-	}
-	__syncthreads();
-	const uint32_t ne = s_n;
-	if (tid == 0)
-		s_base = ne ? atomicAdd(nev, (unsigned long long)ne) : 0;
-	__syncthreads();
-	for (uint32_t i = tid; i < ne; i += kPollWalkThreads)
-		ev[s_base + i] = out[i];
+	su_sort_walk(keys, base, pbits, rec_poll, prios, ms, ms_bmask, ev, ev_cap, nev, ctr,
+	             [](uint32_t e, uint32_t poll, int pr) {
+		             return ((uint64_t)e << 32) | ((uint64_t)(poll & 0xFFFFFFu) << 8) | prio_biased((int8_t)pr);
+	             });
 }
 
 // maxSignal.Merge(newMax_i) for every poll: the events, max-merged (an
@@ -282,14 +217,6 @@ __global__ __launch_bounds__(256) void k_poll_scatter(const uint64_t* __restrict
 				atomicAdd(&tins[t], lc[t]);
 	}
 	block_count(&ctr[kCntOverflow], ovf);
-}
-
-static uint64_t pow2_ge(uint64_t x)
-{
-	uint64_t p = 1;
-	while (p < x)
-		p <<= 1;
-	return p;
 }
 
 }  // namespace syz
@@ -445,8 +372,7 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 	SYZ_TRY(ws_get(ctx, kWsPollEvents, n * 8 + ((uint64_t)K * F + K) * 4 + 64, &dev));
 	dnext = (uint64_t*)dev + n;
 	uint32_t* dpf = (uint32_t*)dnext + (uint64_t)K * F;
-	if (ctx->timing)  // (the call's stream work from its uploads to its last kernel: ctx last_ms)
-		SYZ_HIP(hipEventRecord(ctx->ev[0], s));
+	SYZ_TRY(su_time_begin(ctx));  // (the call's stream work from its uploads to its last kernel: ctx last_ms)
 	if (n) {
 		SYZ_HIP(hipMemcpyAsync(de, elems + poll_off[0], n * 4, hipMemcpyHostToDevice, s));
 		SYZ_HIP(hipMemcpyAsync(dp, prios + poll_off[0], n, hipMemcpyHostToDevice, s));
@@ -464,9 +390,9 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 		uint32_t* base;
 		uint32_t pbits;
 		SYZ_TRY(rp_group(ctx, (const uint64_t*)dx, n, &keys, &base, &pbits, ctx->d_cnt));  // (zeroes the counters)
-		k_poll_part_walk<<<1u << pbits, kPollWalkThreads, 0, s>>>(keys, base, pbits, (const uint32_t*)drp,
-		                                                          (const int8_t*)dp, ms->slots, ms->nbuckets - 1,
-		                                                          (uint64_t*)dev, nev, ctx->d_cnt);
+		k_poll_part_walk<<<1u << pbits, kSuThreads, 0, s>>>(keys, base, pbits, (const uint32_t*)drp, (const int8_t*)dp,
+		                                                    ms->slots, ms->nbuckets - 1, (uint64_t*)dev, n, nev,
+		                                                    ctx->d_cnt);
 		SYZ_HIP(hipGetLastError());
 	}
 	SYZ_TRY(counters_fetch(ctx));
@@ -485,7 +411,7 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 	for (uint32_t g = 0; g < F; g++)
 		if (last[g] < K)
 			entries += syzsig_len(new_max[g]);
-	const uint64_t C = pow2_ge(std::max<uint64_t>(2 * entries, 1024));
+	const uint64_t C = pow2_at_least<uint64_t>(2 * entries, 1024);
 	void *dT, *dtc;
 	SYZ_TRY(ws_get(ctx, kWsPollTable, C * 8 + 64, &dT));
 	SYZ_TRY(ws_get(ctx, kWsPollCounts, ((uint64_t)K + F) * 8 + 64, &dtc));
@@ -537,14 +463,8 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 	SYZ_HIP(hipGetLastError());
 	std::vector<unsigned int> hi((uint64_t)K + F);
 	SYZ_HIP(hipMemcpyAsync(hi.data(), tins, ((uint64_t)K + F) * 4, hipMemcpyDeviceToHost, s));
-	if (ctx->timing)
-		SYZ_HIP(hipEventRecord(ctx->ev[1], s));
+	SYZ_TRY(su_time_end(ctx));
 	SYZ_TRY(counters_fetch(ctx));  // (synchronizes: hi and tg are consumed)
-	if (ctx->timing) {
-		float t = 0;
-		SYZ_HIP(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-		ctx->last_ms = t;
-	}
 	if (ctx->h_cnt[kCntOverflow])
 		return fail(SYZSIG_EIO, "manager_poll_batch: table overflow after reserve (internal error)");
 	fresh.sets.clear();  // everything made here is handed out now

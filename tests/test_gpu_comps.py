@@ -89,9 +89,12 @@ def test_exec_comps_hand_cases(gpu):
 
 @pytest.fixture(scope="module")
 def ragged():
-    """calls of 0, 1, 2, T - 1, T, T + 1, 2 T + 3 and 65535 records; the last
-    drawn from a larger pool, so that most of its triples are distinct"""
-    lens = [0, 1, 2, T - 1, T, T + 1, 2 * T + 3, 65535]
+    """calls of 0 .. 5, T - 1, T, T + 1, 2 T + 3, 3 T (an odd tile count: the
+    last run of a merge pass has no partner), 4 T (a full last tile) and 65535
+    records; the last drawn from a larger pool, so that most of its triples are
+    distinct.  One call: the shorter long calls are copied through the later
+    merge passes of the longest."""
+    lens = [0, 1, 2, 3, 4, 5, T - 1, T, T + 1, 2 * T + 3, 3 * T, 4 * T, 65535]
     a, _ = synth.comparisons(11, lens[:-1], OUT)
     b, _ = synth.comparisons(12, lens[-1:], OUT, pool=700)
     comps = np.concatenate([a, b])

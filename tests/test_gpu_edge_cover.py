@@ -87,6 +87,37 @@ def test_edge_cover_lengths_and_contents(gpu, dedup):
     np.testing.assert_array_equal(cover, ecover)
 
 
+def _one_program(gpu, chunks, dedup=True):
+    """the chunks as the calls of one completed program -> (cover, cnt), checked against the restatement"""
+    lens = np.array([c.size for c in chunks], np.uint32)
+    starts = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64)
+    pcs = np.concatenate(chunks)
+    prog_call = np.array([0, lens.size], np.uint32)
+    completed = np.array([lens.size], np.uint32)
+    cover, cnt = _run(gpu, pcs, starts, lens, prog_call, completed, dedup)
+    ecover, ecnt = CR.edge_cover(pcs, starts, lens, prog_call, completed, dedup, fill=FILL)
+    np.testing.assert_array_equal(cnt, ecnt)
+    np.testing.assert_array_equal(cover, ecover)
+    return cover, cnt
+
+
+def test_edge_cover_pad_sizes_and_tile_counts(gpu):
+    """3, 4 and 5 keys around the smallest padded sort; 3 T keys: an odd tile
+    count, so the last run of a merge pass has no partner; 4 T: a full last
+    tile and a power-of-two run count.  One call, so that the shorter long
+    segments are copied through the later passes of the longest."""
+    rng = np.random.default_rng(23)
+    lens = [3, 4, 5, 3 * T, 4 * T]
+    _, cnt = _one_program(gpu, [_contents(kind, n, rng) for n, kind in zip(lens, ["desc", "span", "dups", "span", "dups"])])
+    assert cnt[0] == 3 and cnt[3] > 2 * T
+
+
+def test_edge_cover_one_pc_repeated_past_two_tiles(gpu):
+    """duplicates across every tile and run boundary: one survivor"""
+    cover, cnt = _one_program(gpu, [_contents("equal", 2 * T + 1, None)])
+    assert cnt.tolist() == [1] and cover[0] == 0x81000010
+
+
 def test_edge_cover_aborts(gpu):
     rng = np.random.default_rng(5)
     nprog, cpp = 16, 8

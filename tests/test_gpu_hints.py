@@ -85,6 +85,18 @@ def test_shrink_expand_random_queries(gpu):
     assert (per_q > 0).mean() > 0.5 and (per_q == 0).any()  # most queries have candidates, some have none
 
 
+def test_shrink_expand_candidates_at_the_tile_edge(gpu):
+    """Queries with exactly T and T + 1 candidates: only the width-8 variant of
+    v finds a key, every pair of it is a candidate and none is a special int,
+    so the first query's segment fills the LDS tile and the second is the
+    shortest one that goes through the tiles and one merge pass."""
+    v = 0x1122334455667788
+    maps = [{v: {(1 << 48) + 3 * i for i in range(T)}}, {v: {(1 << 48) + 3 * i for i in range(T + 1)}}]
+    exp = [R.shrink_expand(v, m, SPECIAL_INTS) for m in maps]
+    assert [len(x) for x in exp] == [T, T + 1]
+    assert run(gpu, maps, [0, 1], [v, v], SPECIAL_INTS) == exp
+
+
 def test_shrink_expand_candidates_past_the_tile_and_erange(gpu):
     rng = np.random.default_rng(33)
     vs = set(int(x) for x in rng.integers(0, 1 << 40, 3 * T))  # widths 8, 4, 2 and 1 all find key 0x34

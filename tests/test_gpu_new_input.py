@@ -125,16 +125,18 @@ def test_new_input_sequential_path_vs_reference_loop(gpu, case):
 
 
 def test_new_input_key_group_sizes_and_long_paths(gpu):
-    """Keys whose accepted rows hold 0, 1, 2, T-1, T, T+1 and 2T+3 entries
-    (T = SYZSIG_CORPUS_TILE, the LDS sort's tile; past it a key is tile-sorted
-    and rank-merged through the workspace: two passes for 2T+3), the entries
+    """Keys whose accepted rows hold 0, 1, 2, 3, T-1, T, T+1, 2T+3, 3T and 4T
+    entries (T = SYZSIG_CORPUS_TILE, the LDS sort's tile; past it a key is
+    tile-sorted and rank-merged through the workspace: two passes for 2T+3 to
+    4T; 3T: an odd tile count, the last run of the first pass has no partner;
+    4T: a full last tile; T+1 is copied through the second pass), the entries
     split over two rows that share elements, with duplicates inside a row; and
     one key whose covers hold 2 * SYZSIG_COVER_TILE + 3 PCs (cover.hip's long
     path).  Asserts that the long paths were taken."""
     from syzkaller_amd._lib import SYZSIG_CORPUS_TILE as T, SYZSIG_COVER_TILE as CT
 
     rng = np.random.default_rng(3)
-    sizes = [0, 1, 2, T - 1, T, T + 1, 2 * T + 3]
+    sizes = [0, 1, 2, 3, T - 1, T, T + 1, 2 * T + 3, 3 * T, 4 * T]
     rows = []
     for k, sz in enumerate(sizes):
         base = 100_000 * (k + 1)
@@ -162,7 +164,7 @@ def test_new_input_key_group_sizes_and_long_paths(gpu):
     assert acc.tolist() == [int(r[1][0].size > 0) for r in rows]  # every non-empty row is live
     live = {k: sum(r[1][0].size for r in rows if r[0] == k) for k in range(len(sizes))}
     assert [live[k] for k in range(len(sizes))] == sizes
-    assert stats == {"sequential": 0, "large_keys": 2, "merge_passes": 2, "large_covers": 1}
+    assert stats == {"sequential": 0, "large_keys": 4, "merge_passes": 2, "large_covers": 1}
 
 
 def _raw_call(eng, cs, cc, keys, flags, sig_off, elems, prios, cov_off, cover, nkeys, sig_cap, cov_cap, bufs):

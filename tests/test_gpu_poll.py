@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.table_keys import fmix32_inv_np, fmix32_np
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +48,70 @@ def test_poll_batch_vs_sequential_oracle(gpu, monkeypatch, seed, F, K, U, n, lim
     for g in range(F):
         assert (nm[g].to_dict() if not nm[g].is_nil() else {}) == onm[g].to_dict(), f"fuzzer {g}"
         assert nm[g].is_nil() == onm[g].is_nil() or onm[g].Len() == 0
+
+
+PBITS = 7  # csrc/recs.hip rp_pbits for a batch of at most 2^17 entries: partition = the top 7 bits of fmix32(e)
+GROUP_CAP = 2048  # csrc/internal.h kRpGroupCap
+
+
+def _in_partition(rng, p, n):
+    """n distinct elements of element partition p"""
+    r = rng.choice(1 << (32 - PBITS), size=n, replace=False).astype(np.uint64)
+    return fmix32_inv_np(((np.uint64(p) << np.uint64(32 - PBITS)) | r).astype(np.uint32))
+
+
+@pytest.mark.parametrize("case", ["1_2_3", "cap"])
+def test_poll_batch_partition_sizes(gpu, case):
+    """The LDS sort of k_poll_part_walk at its edges: partitions of exactly 1,
+    2 and 3 entries (sorts of 1, 2 and 4 keys, the last one padded), and a
+    partition of exactly kRpGroupCap entries (the largest batched case: the
+    whole tile, no pad)."""
+    from syzkaller_amd import signal as S
+
+    rng = np.random.default_rng(41)
+    F = 3
+    if case == "1_2_3":
+        K = 6
+        a, b, c, d = (int(_in_partition(rng, p, 1)[0]) for p in (0, 1, 2, 2))
+        special = {0: [(b, 1)], 1: [(c, 3), (c, -1)], 2: [(a, 2)], 3: [(b, 4)], 4: [(d, 0)]}
+        want = {0: 1, 1: 2, 2: 3}
+        m0_extra = ([b], [2])
+        fill = [int(x) for x in range(3, 1 << PBITS)]
+    else:
+        K = 8
+        hot = _in_partition(rng, 9, GROUP_CAP // K)
+        special = {i: list(zip(hot.tolist(), rng.integers(-3, 5, hot.size).tolist())) for i in range(K)}
+        want = {9: GROUP_CAP}
+        m0_extra = (hot[::2].tolist(), rng.integers(-3, 5, hot[::2].size).tolist())
+        fill = [p for p in range(1 << PBITS) if p != 9]
+    pool = np.concatenate([_in_partition(rng, p, 4) for p in fill])
+    polls = []
+    for i in range(K):
+        e = rng.choice(pool, size=200).astype(np.uint32)
+        p = rng.integers(-3, 5, e.size).astype(np.int8)
+        se, sp = zip(*special[i]) if special.get(i) else ((), ())
+        at = rng.integers(0, e.size + 1)  # the chosen entries in order, somewhere inside the Serial
+        polls.append((int(rng.integers(0, F)), (np.concatenate([e[:at], np.array(se, np.uint32), e[at:]]),
+                                                np.concatenate([p[:at], np.array(sp, np.int8), p[at:]]))))
+    m0e = np.concatenate([rng.choice(pool, size=150, replace=False), np.array(m0_extra[0], np.uint32)]).astype(np.uint32)
+    m0 = (m0e, np.concatenate([rng.integers(-3, 5, 150), np.array(m0_extra[1])]).astype(np.int8))
+    # the partitions' sizes, before anything runs on the device
+    entries = np.concatenate([e for _, (e, _) in polls])
+    assert (entries.size >> PBITS) <= 1024  # rp_pbits stays at PBITS
+    sizes = np.bincount(fmix32_np(entries) >> np.uint32(32 - PBITS), minlength=1 << PBITS)
+    assert all(sizes[p] == n for p, n in want.items()) and sizes.max() <= GROUP_CAP
+    ms = S.Serial(*m0).Deserialize(gpu.eng)
+    nm = [S.Signal(None, gpu.eng) for _ in range(F)]
+    replies = S.manager_poll(ms, nm, [(f, S.Serial(e, p)) for f, (e, p) in polls], gpu.eng)
+    oms = O.deserialize(*m0)
+    onm = [O.OSig() for _ in range(F)]
+    for i, (f, ser) in enumerate(polls):
+        re, rp = O.poll(oms, onm, f, ser)
+        got = dict(zip(replies[i].Elems.tolist(), replies[i].Prios.tolist()))
+        assert got == dict(zip(re.tolist(), rp.tolist())), f"reply {i}"
+    assert ms.to_dict() == oms.to_dict()
+    for g in range(F):
+        assert (nm[g].to_dict() if not nm[g].is_nil() else {}) == onm[g].to_dict(), f"fuzzer {g}"
 
 
 def test_poll_batch_empty_and_nil_max(gpu):
