@@ -192,10 +192,25 @@ def main(only=None):
     # 5. a call at the per-call limit region boundary (kCoverSize - 1 PCs)
     big = synth_programs(synth.synth_default(region_log2=14), 1, 1, (262143, 262143), 14, prog_base=300)
     out["executor_big"] = big
+    # 6. traces built for the kernel's structure (tests/edge_traces.py): dense
+    #    conflicts at K2's bin and mark-word boundaries, five home sets of 8
+    #    programs; call lengths at K1's chunk / group / buffer edges and
+    #    cover_check failures by position (with the sparse call_start layout)
+    from tests import edge_traces as ET
+
+    out["executor_dense"] = [p for name in ET.HOME_SETS for p in ET.dense_set(name)]
+    geo, gaps = ET.geometry_programs()
+    ab, ab_gaps, _ = ET.abort_position_programs()
+    gaps.update({(len(geo) + p, c): g for (p, c), g in ab_gaps.items()})
+    out["executor_geometry"] = (geo + ab, gaps)
     for name, programs in out.items():
         if only and name not in only:
             continue
-        fx = pack(programs)
+        if isinstance(programs, tuple):  # (programs, gaps): PCs between the calls that belong to none
+            programs, gaps = programs
+            fx = ET.pack(programs, gaps)
+        else:
+            fx = pack(programs)
         fx.update(expected(fx, programs))
         np.savez_compressed(os.path.join(HERE, name + ".npz"), **fx)
         print(f"{name}: {len(programs)} programs, {fx['call_len'].size} calls, {fx['pcs'].size} PCs, "

@@ -68,7 +68,7 @@ def write_slots(s, ps, h):
     return [(h + k) % M for k in range(4) if ps >> k & 1]
 
 
-def round_chunk(T, ch, binsh=3, seq_max=0, mark_all=False):
+def round_chunk(T, ch, binsh=3, seq_max=0, mark_all=False, info=None):
     """One chunk through the rounds; returns (emitted flags, rounds).  Once a
     round leaves at most seq_max lanes pending, they go to edge.hip's tail
     (SYZ_EDGE_SEQ): in passes, a pending signal whose window no earlier pending
@@ -76,7 +76,10 @@ def round_chunk(T, ch, binsh=3, seq_max=0, mark_all=False):
     because every write lies in its writer's window, given the rounds'
     invariant that the pending lanes, run in order on the table as it stands,
     give the sequential outcome.  mark_all (SYZ_EDGE_MARKALL): every pending
-    lane marks in the first pass, so one pass is the fixed point."""
+    lane marks in the first pass, so one pass is the fixed point.  A dict
+    given as `info` receives what the first round saw: its writers, its
+    duplicates (the count the kernel reports to the host's mode choice) and the
+    lanes it left pending."""
     n, pend, emit, rounds = len(ch), list(range(len(ch))), [False] * len(ch), 0
     while pend:
         if rounds and len(pend) <= seq_max:
@@ -137,6 +140,8 @@ def round_chunk(T, ch, binsh=3, seq_max=0, mark_all=False):
                 T[ev[i][1]] = ch[i]
                 emit[i] = True
         assert len(nxt) < len(pend)  # the earliest pending lane always finishes
+        if info is not None and rounds == 1:
+            info.update(writers=[i for i in pend if ev[i][0]], dups=sum(not ev[i][0] for i in pend), pending=len(nxt))
         pend = nxt
     return emit, rounds
 
@@ -338,3 +343,168 @@ def test_clear_race_trace_shape():
             got, rounds = round_chunk(Tp, ch, seq_max=0, mark_all=True)
             assert got == [seq_dedup(Ts, s) for s in ch]
             assert (rounds == 1) == (q % 2 == 0), (p, q, rounds)
+
+
+# ---- traces built for the kernel's structure (tests/edge_traces.py) ----
+from tests import edge_traces as ET  # noqa: E402
+
+MODES = [False, True]  # mark_all
+
+
+def first_round(T, ch, mark_all=False):
+    """What the first round of chunk `ch` on table T sees and leaves (T is not
+    changed): {"writers": lanes, "dups": count, "pending": count}."""
+    info = {}
+    round_chunk(list(T), ch, seq_max=len(ch), mark_all=mark_all, info=info)
+    return info
+
+
+def call_sigs(trace):
+    """write_coverage_signal's K1 (executor.h:497-505): sig_i = (u32)pc_i ^ hash((u32)pc_{i-1})."""
+    prev, sigs = 0, []
+    for x in np.asarray(trace, np.uint64).tolist():
+        sigs.append((x & 0xFFFFFFFF) ^ prev)
+        prev = exec_hash(x & 0xFFFFFFFF)
+    return sigs
+
+
+def program_chunks(prog):
+    """(call, chunk offset, the chunk's signals) over a program's calls."""
+    for c, (_, trace) in enumerate(prog):
+        sigs = call_sigs(trace)
+        for c0 in range(0, len(sigs), 256):
+            yield c, c0, sigs[c0: c0 + 256]
+
+
+def check_rounds(programs, seq_max, mark_all):
+    for p, prog in enumerate(programs):
+        Tp, Ts = [0] * M, [0] * M
+        for c, c0, ch in program_chunks(prog):
+            got, _ = round_chunk(Tp, ch, seq_max=seq_max, mark_all=mark_all)
+            assert got == [seq_dedup(Ts, s) for s in ch], (p, c, c0)
+            assert Tp == Ts, (p, c, c0)
+
+
+@pytest.mark.parametrize("seq_max", SEQ_MAX)
+@pytest.mark.parametrize("mark_all", MODES)
+@pytest.mark.parametrize("name", sorted(ET.HOME_SETS))
+def test_rounds_dense_conflicts(name, mark_all, seq_max):
+    check_rounds(ET.dense_set(name), seq_max, mark_all)
+
+
+@pytest.mark.parametrize("seq_max", SEQ_MAX)
+@pytest.mark.parametrize("mark_all", MODES)
+def test_rounds_call_length_geometry(mark_all, seq_max):
+    check_rounds(ET.geometry_programs()[0], seq_max, mark_all)
+
+
+@pytest.mark.parametrize("seq_max", SEQ_MAX)
+@pytest.mark.parametrize("mark_all", MODES)
+def test_rounds_abort_positions(mark_all, seq_max):
+    """(replayed over all calls, as for the abort fixture: the rounds are
+    checked against sequential dedup, not against the abort)"""
+    check_rounds(ET.abort_position_programs()[0], seq_max, mark_all)
+
+
+@pytest.mark.parametrize("seq_max", SEQ_MAX)
+@pytest.mark.parametrize("mark_all", MODES)
+def test_rounds_stride_batch(mark_all, seq_max):
+    progs, origin = ET.stride_batch()
+    check_rounds(progs[: ET.GRID_CAP], seq_max, mark_all)  # the rest are copies
+
+
+@pytest.mark.parametrize("name", sorted(ET.HOME_SETS))
+def test_dense_set_shape(name):
+    """Conditions on the input, so that the dense sets reach what they were
+    built for: rounds past the tail bound (more than 32 lanes pending after a
+    first round; SYZ_EDGE_SEQ = 32), the tail (1..32 pending), re-run passes
+    (3 or more rounds in the passes mode), calls that are mostly targets, the
+    filler window far from the homes, and a first-round writer at every home
+    whose window crosses a bin or a mark word."""
+    homes, far = ET.HOME_SETS[name]
+    progs, counts = ET.dense_set(name, meta=True)
+    # (windows: a home's h..h+3, the fillers' far[0]..far[1]+2)
+    assert all(min((far[0] - h - 3) % M, (h - far[1] - 2) % M) >= 1024 for h in homes)
+    over_tail = in_tail = three_rounds = False
+    writer_homes = set()
+    for prog, cnt in zip(progs, counts):
+        T = [0] * M
+        for c, c0, ch in program_chunks(prog):
+            if cnt[c] is not None:
+                if c0 == 0:
+                    assert cnt[c] >= 0.55 * len(prog[c][1]), (name, c, cnt[c], len(prog[c][1]))
+                    assert sum(s % M in homes for s in call_sigs(prog[c][1])) == cnt[c]
+                info = first_round(T, ch)
+                over_tail |= info["pending"] > 32
+                in_tail |= 1 <= info["pending"] <= 32
+                writer_homes |= {ch[i] % M for i in info["writers"]}
+                three_rounds |= round_chunk(list(T), ch, seq_max=0)[1] >= 3
+            for s in ch:
+                seq_dedup(T, s)
+    assert over_tail and in_tail and three_rounds
+    assert set(ET.boundary_homes(homes)) <= writer_homes
+
+
+def test_geometry_and_stride_shape():
+    progs, gaps = ET.geometry_programs()
+    assert [len(t) for _, t in progs[-1]] == ET.LENGTHS
+    assert [[len(t) for _, t in p] for p in progs[:-1]] == [[n, n] for n in ET.LENGTHS]
+    pcs, cs, cl, pc = ET.flat(progs, gaps)
+    sparse = slice(int(pc[-2]), int(pc[-1]))
+    gap = cs[sparse][1:] - (cs[sparse][:-1] + cl[sparse][:-1])
+    assert gap.min() >= 1 and gap.max() <= 7
+    # the second call of a pair both matches and overwrites what the first left
+    for p in (progs[ET.LENGTHS.index(2048)], progs[ET.LENGTHS.index(2100)]):
+        T = [0] * M
+        for s in call_sigs(p[0][1]):
+            seq_dedup(T, s)
+        first = set(x for x in T if x)
+        emitted = [seq_dedup(T, s) for s in call_sigs(p[1][1])]
+        assert not all(emitted) and first - set(T)
+    sprogs, origin = ET.stride_batch()
+    assert len(sprogs) == 2100 > 2 * ET.GRID_CAP
+    assert all(sprogs[p] is sprogs[origin[p]] for p in range(2100))
+    assert origin[1024:2048].tolist() == list(range(1024)) and origin[2048:].tolist() == list(range(52))
+    assert all(24 <= len(t) <= 48 for p in range(1024) if p % 10 for _, t in sprogs[p])
+
+
+def test_abort_positions_give_constructed_completed():
+    from oracle import oracle as O
+
+    progs, gaps, completed = ET.abort_position_programs()
+    pcs, cs, cl, pc = ET.flat(progs, gaps)
+    sigs, cnt, comp = O.exec_batch(pcs, cs, cl, pc)
+    np.testing.assert_array_equal(comp, completed)
+    assert comp[-1] == len(progs[-1])  # failing PCs in the gaps abort nothing
+    for p in range(len(progs)):
+        a, b = int(pc[p]), int(pc[p + 1])
+        assert (cnt[a: a + int(comp[p])] > 0).all() and (cnt[a + int(comp[p]): b] == 0).all()
+    for (p, c), g in gaps.items():  # the gap program's gaps do hold failing PCs
+        assert not any(0xFFFFFFFF80000000 <= int(x) < 0xFFFFFFFFFF000000 for x in g)
+
+
+def first_round_dup_share(pcs, cs, cl, pc):
+    """The figure the host's mode choice uses (edge.hip kEdgeMarkAllMaxDupPct):
+    first-round duplicates of every chunk over the PCs of the launch."""
+    dups = 0
+    for p in range(pc.size - 1):
+        T = [0] * M
+        for c in range(int(pc[p]), int(pc[p + 1])):
+            sigs = call_sigs(pcs[int(cs[c]): int(cs[c]) + int(cl[c])])
+            for c0 in range(0, len(sigs), 256):
+                ch = sigs[c0: c0 + 256]
+                dups += first_round(T, ch)["dups"]
+                for s in ch:
+                    seq_dedup(T, s)
+    return dups / pcs.size
+
+
+def test_mode_choice_primers_lie_on_both_sides():
+    """test_edge_mode_choice_follows_previous_launch primes the library's mode
+    choice with these two batches: one well above, one below 5 % first-round
+    duplicates.  (Two programs of each: the programs of a batch are drawn
+    alike.)"""
+    pcs, cs, cl, pc = ET.dup_heavy_batch()
+    assert first_round_dup_share(pcs[: int(cs[16])], cs[:16], cl[:16], pc[:3]) > 0.25
+    pcs, cs, cl, pc = clear_race_trace(16)
+    assert first_round_dup_share(pcs[: int(cs[2])], cs[:2], cl[:2], pc[:3]) < 0.01
