@@ -62,8 +62,8 @@ int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
 /* With timing on: device time (ms, HIP events on the context stream) of the
  * kernels of the last syzsig_edge_derive_dev / syzsig_minimize_dev call, or the
  * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev,
- * syzsig_triage_cover_dev, syzsig_exec_comps_dev, syzsig_comp_map_dev or
- * syzsig_shrink_expand_dev call (uploads / first kernel to its last kernel,
+ * syzsig_triage_cover_dev, syzsig_triage_items_dev, syzsig_exec_comps_dev,
+ * syzsig_comp_map_dev or syzsig_shrink_expand_dev call (uploads / first kernel to its last kernel,
  * including the host round trips between); for syzsig_manager_new_input_batch
  * the host wall time of the call, which ends synchronised. */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
@@ -465,6 +465,75 @@ int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_t runs, con
                             const uint8_t* d_run_exec, const uint32_t* d_cover, uint64_t ncover,
                             const uint64_t* d_run_cover_start, const uint32_t* d_run_cover_len,
                             uint64_t* d_item_cover_off, uint32_t* d_item_cover, uint64_t cap, uint64_t* n_out);
+
+/* ---- syz-fuzzer/proc.go:232-245 and :107-111: a batch's triage items, their
+ * inputSignal and newSignal ----
+ * The step between syzsig_triage_batch and syzsig_triage_runs_dev.  The batch
+ * is d_sigs / nrec / d_call_start / d_call_len / d_call_prio / ncalls as
+ * syzsig_triage_batch took them, d_call_new (an input here) what it wrote:
+ * every call with call_new != 0 is one WorkTriage (proc.go:232-245).  Item i is
+ * the i-th such call in ascending call index, the order execute enqueues them
+ * in; *n_items = their number.  corpus_signal = fuzzer.corpusSignal (NULL = nil:
+ * everything is new).  All array pointers are device pointers.  Per item:
+ *  - d_item_call[i] = its call, d_item_prio[i] = (int8)call_prio[call], as
+ *    FromRaw casts signalPrio's value (signal.go:35);
+ *  - inputSignal = FromRaw(item.info.Signal, prio) (:107) as CSR: the call's
+ *    distinct elements, ascending (one fixed instance of Serialize's map
+ *    order), at d_input_elems[input_off[i] .. input_off[i + 1]); every one
+ *    carries d_item_prio[i].  input_off / input_elems / item_prio are
+ *    RPCInput.Signal (:172) and what syzsig_corpus_add_inputs_dev takes;
+ *  - newSignal = corpusSignal.Diff(inputSignal) (:108, signal.go:73-88) as CSR,
+ *    exactly what syzsig_triage_runs_dev reads: the elements e of inputSignal
+ *    except those that corpusSignal holds with corpus[e] >= item_prio[i]
+ *    (compared as int8), ascending, at d_elems / d_prios[item_off[i] ..
+ *    item_off[i + 1]).  An item with nothing new keeps an empty range, which
+ *    syzsig_triage_runs_dev drops as :109-111 does.
+ * A flagged call of no records gives two empty ranges (FromRaw of an empty
+ * slice is nil, Diff of nil is nil).  Both offset arrays have n_items + 1
+ * entries (item_cap + 1 as capacity).
+ * Batch semantics: every item's Diff is against corpusSignal as passed in --
+ * the interleaving in which every Proc reaches :108 before any reaches :176
+ * (the three re-executions lie between).  One item per call gives the strictly
+ * sequential order.
+ * Capacities: item_cap (items), input_cap (entries of d_input_elems), new_cap
+ * (entries of d_elems / d_prios).  The three needed totals always go to
+ * *n_items / *n_input / *n_new; if one exceeds its capacity nothing is written
+ * to any output array and the result is SYZSIG_ERANGE: grow and call again.
+ * SYZSIG_EINVAL (nothing written): a NULL required argument, a call range
+ * outside [0, nrec).  SYZSIG_ERANGE: a flagged call of 2^31 or more records,
+ * 2^32 or more calls.
+ * SYZSIG_ITEMS_TILE: a call of at most this many records is sorted in LDS by
+ * one workgroup; a longer one is tile-sorted and rank-merged through the
+ * context's workspace in HBM. */
+#define SYZSIG_ITEMS_TILE 4096
+int syzsig_triage_items_dev(syzsig_ctx* ctx, const uint32_t* d_sigs, uint64_t nrec, const uint64_t* d_call_start,
+                            const uint32_t* d_call_len, const uint8_t* d_call_prio, uint64_t ncalls,
+                            const uint8_t* d_call_new, const syzsig_set* corpus_signal, uint32_t* d_item_call,
+                            int8_t* d_item_prio, uint64_t item_cap, uint64_t* d_input_off, uint32_t* d_input_elems,
+                            uint64_t input_cap, uint64_t* d_item_off, uint32_t* d_elems, int8_t* d_prios,
+                            uint64_t new_cap, uint64_t* n_items, uint64_t* n_input, uint64_t* n_new);
+/* Which paths the context's last syzsig_triage_items_dev took (tests, tuning;
+ * results never depend on them): out[0] = items, out[1] = items longer than
+ * SYZSIG_ITEMS_TILE, out[2] = the rank-merge passes over them, out[3] = probes
+ * of corpusSignal (one per distinct element of an item; 0 for a nil set). */
+int syzsig_triage_items_stats(syzsig_ctx* ctx, uint64_t out[4]);
+
+/* ---- syz-fuzzer/fuzzer.go:446-460 addInputToCorpus, over the items that
+ * triageInput kept ----
+ * d_input_off / d_input_elems / d_item_prio as syzsig_triage_items_dev wrote
+ * them (n_items items, n_input = the entries of d_input_elems: a range that is
+ * reversed or ends past it is SYZSIG_EINVAL); d_item_keep[i] != 0 = item i
+ * reached :176 (NULL = all; syzsig_triage_runs_dev's item_keep and the caller's
+ * minimization decide).  For every kept item whose sign is not empty (:454):
+ * corpusSignal.Merge(sign); maxSignal.Merge(sign) (:456-457).  Max-merge
+ * commutes, so the batch is the sequential loop exactly.  A NULL *corpus_signal
+ * or *max_signal is nil and is allocated only if some kept item is non-empty
+ * (signal.go:117-131).  Room is reserved in both tables before the one launch
+ * that commits; an error before it leaves both sets' contents (and NULL sets
+ * NULL) as they were.  The two sets must be distinct (SYZSIG_EINVAL). */
+int syzsig_corpus_add_inputs_dev(syzsig_ctx* ctx, const uint64_t* d_input_off, const uint32_t* d_input_elems,
+                                 uint64_t n_input, const int8_t* d_item_prio, uint64_t n_items,
+                                 const uint8_t* d_item_keep, syzsig_set** corpus_signal, syzsig_set** max_signal);
 
 /* ---- pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output regions ----
  * Program p's output region (executor.h:566-604 records, the executor's shmem

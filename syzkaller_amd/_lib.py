@@ -29,6 +29,7 @@ SYZSIG_COVER_DEDUP = 1
 SYZSIG_COVER_TILE = 4096  # include/syzsig.h: longer segments leave the one-workgroup LDS sort
 SYZSIG_COMPS_TILE = 2048  # the same for the comparison hints' keys (comps.hip)
 SYZSIG_CORPUS_TILE = 2048  # the same for a corpus key's entries in the NewInput batch (corpus.hip)
+SYZSIG_ITEMS_TILE = 4096  # the same for a triage item's records (items.hip)
 SYZSIG_INPUT_PRESENT = 1  # a NewInput batch row that is the key's old corpus entry
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
@@ -144,6 +145,10 @@ SIGNATURES = {
     "syzsig_edge_cover_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, c_uint32, _P, _P]),
     "syzsig_triage_cover_dev": (c_int, [_P, c_uint64, c_uint32, _P, _P, _P, _P, _P, _P, c_uint64, _P, _P, _P, _P,
                                         c_uint64, POINTER(c_uint64)]),
+    "syzsig_triage_items_dev": (c_int, [_P, _P, c_uint64, _P, _P, _P, c_uint64, _P, _P, _P, _P, c_uint64, _P, _P, c_uint64,
+                                        _P, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "syzsig_triage_items_stats": (c_int, [_P, _P]),
+    "syzsig_corpus_add_inputs_dev": (c_int, [_P, _P, _P, c_uint64, _P, c_uint64, _P, _PP, _PP]),
     "syzsig_exec_comps_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P, _P]),
     "syzsig_comp_map_dev": (c_int, [_P, _P, c_uint64, _P, _P, _P, c_uint64, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     "syzsig_shrink_expand_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, _P, c_uint64, _P, c_uint32, _P, _P,

@@ -74,7 +74,7 @@ struct CmOutComps {
 		return false;
 	}
 	// survivors << 32 | words
-	__device__ __forceinline__ uint64_t weight(const SuWords<3>& k) const
+	__device__ __forceinline__ uint64_t weight(uint64_t, const SuWords<3>& k) const
 	{
 		if (ignore(k.w[0], k.w[1], k.w[2]))
 			return 0;
@@ -82,7 +82,7 @@ struct CmOutComps {
 	}
 	// executor.h:823-859.  The low 32 bits of a sign extension from 1, 2 or 4
 	// bytes are what leaves for those sizes.
-	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const SuWords<3>& k) const
+	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const SuWords<3>& k, uint64_t) const
 	{
 		uint32_t* o = out + 5 * call_start[seg] + (uint32_t)pos;
 		const uint32_t sz = (uint32_t)k.w[0] & kCmpSizeMask;

@@ -136,7 +136,7 @@ enum WsSlot : int {
 	kWsNiCoverOut = 35,
 	kWsMinCursor = 36,
 	kWsNiOut = 36,
-	kWsSuStage2 = 37,  // comps.hip (see kWsSuMeta)
+	kWsSuStage2 = 37,  // comps.hip, items.hip (see kWsSuMeta)
 	kWsNiGroupCover = 38,
 	// manager poll (poll.hip) | the NewInput batch's acceptance and uploads (corpus.hip)
 	kWsPollTargets = 39,
@@ -155,7 +155,8 @@ enum WsSlot : int {
 	kWsNiEvents = 46,
 	kWsPollCounts = 47,
 	kWsNiAccepted = 47,
-	// the sort-unique of cover.hip and of the comparison hints (comps.hip, with kWsSuStage2)
+	// the sort-unique of cover.hip, of the comparison hints and of the triage items (comps.hip,
+	// items.hip: with kWsSuStage2)
 	// | rp_group, the LDS grouping for Poll (recs.hip)
 	kWsSuMeta = 48,
 	kWsRpgSeg = 48,
@@ -243,6 +244,7 @@ struct syzsig_ctx {
 	bool step_own_timed = false, step_src_timed = false, step_back_timed = false;
 	hipEvent_t ev_step[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	uint64_t ni_stats[4] = {0, 0, 0, 0};  // syzsig_new_input_stats: the last NewInput batch's paths (corpus.hip)
+	uint64_t it_stats[4] = {0, 0, 0, 0};  // syzsig_triage_items_stats: the last triage_items call's paths (items.hip)
 };
 
 struct syzsig_set {

@@ -1,6 +1,6 @@
 // segsort.h -- the segmented sort-unique and the sort-and-walk, once: shared by
-// cover.hip (u32 keys), comps.hip (keys of 1-3 u64 words), corpus.hip and
-// poll.hip (u64 keys = keys of one word).  Everything here is a template or
+// cover.hip and items.hip (u32 keys), comps.hip (keys of 1-3 u64 words),
+// corpus.hip and poll.hip (u64 keys = keys of one word).  Everything here is a template or
 // inline: each translation unit instantiates what it launches.
 //
 // Per segment: sort ascending, drop equal neighbours, hand the survivors to an
@@ -33,8 +33,9 @@
 // A key type (SuU32, SuU64<W>) gives the value type T, lt / eq, the pad key
 // and the key's layout in the HBM sort buffers (get / put over Word).  A tile
 // type gives the key, the tile size and the tile's LDS routines: SuWordsTile
-// is the plain one (struct-of-arrays tile, su_bitonic); cover.hip brings its
-// tuned u32 routines as a tile type of its own.
+// is the plain one (struct-of-arrays tile, su_bitonic) and SuU32Tile the same
+// for u32 keys; cover.hip brings its tuned u32 routines as a tile type of its
+// own.
 //
 // su_sort_walk is the other user of the plain sort: Poll's and NewInput's
 // workgroup-per-partition event walk (k_poll_part_walk, k_ni_walk).
@@ -197,8 +198,8 @@ struct SuOutKeys {
 	{
 		return out + out_pos[seg * pos_stride] * Key::kWords;
 	}
-	__device__ __forceinline__ uint64_t weight(const typename Key::T&) const { return 1; }
-	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const typename Key::T& k) const
+	__device__ __forceinline__ uint64_t weight(uint64_t, const typename Key::T&) const { return 1; }
+	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const typename Key::T& k, uint64_t) const
 	{
 		Key::put(dst(seg), pos, k);
 	}
@@ -288,7 +289,8 @@ __device__ __forceinline__ void su_bitonic(Lds& t, uint32_t N)
 
 // The survivors of the sorted keys 0 .. n) -- key i survives iff i == 0 or it
 // differs from key i - 1 -- handed to the policy at the exclusive sums of their
-// weights; returns the total (workgroup-wide, uniform).
+// weights, each with its own weight (nonzero: what weight() found out about the
+// key need not be found out again); returns the total (workgroup-wide, uniform).
 template <typename Key, typename Pol, typename Get>
 __device__ __forceinline__ uint64_t su_unique_write(uint32_t n, uint64_t seg, const Pol& pol, Get get)
 {
@@ -303,7 +305,7 @@ __device__ __forceinline__ uint64_t su_unique_write(uint32_t n, uint64_t seg, co
 		if (i < n) {
 			k = get(i);
 			if (i == 0 || !Key::eq(k, get(i - 1)))
-				wt = pol.weight(k);
+				wt = pol.weight(seg, k);
 		}
 		const uint64_t incl = wave_incl_scan(wt);
 		if (lane_id() == 63)
@@ -316,7 +318,7 @@ __device__ __forceinline__ uint64_t su_unique_write(uint32_t n, uint64_t seg, co
 			tot += s_w[it][x];
 		}
 		if (wt)
-			pol.put(seg, run + wb + incl - wt, k);
+			pol.put(seg, run + wb + incl - wt, k, wt);
 		run += tot;
 	}
 	return run;
@@ -387,6 +389,56 @@ struct SuWordsTile {
 	static __device__ __forceinline__ uint64_t unique_buf(uint32_t n, uint64_t seg, const Pol& pol, const uint64_t* s)
 	{
 		return su_unique_write<Key>(n, seg, pol, [&](uint32_t i) { return Key::get(s, i); });
+	}
+};
+
+// The plain tile of kTileKeys u32 keys (sources of u32 words): one array in
+// LDS, 4 kTileKeys bytes.
+template <uint32_t kTileKeys>
+struct SuU32Tile {
+	using Key = SuU32;
+	static constexpr uint32_t kTile = kTileKeys, kAlign = 1, kMinPad = 1;
+	struct Lds {
+		uint32_t k[kTileKeys];
+		__device__ __forceinline__ uint32_t get(uint32_t i) const { return k[i]; }
+		__device__ __forceinline__ void set(uint32_t i, uint32_t x) { k[i] = x; }
+	};
+	static __device__ __forceinline__ void load(const SuSegs& S, uint64_t seg, uint32_t lo, uint32_t n, Lds& t)
+	{
+		uint64_t o = 0;
+		for (uint32_t r = 0; r < S.R; r++) {
+			const uint32_t len = S.src_len[seg * S.R + r];
+			const uint64_t a = std::max<uint64_t>(lo, o), b = std::min<uint64_t>((uint64_t)lo + n, o + len);
+			if (a < b) {
+				const uint32_t* p =
+					reinterpret_cast<const uint32_t*>(S.src) + (S.src_start[seg * S.R + r] + (a - o)) * S.stride;
+				const uint32_t d = (uint32_t)(a - lo), cnt = (uint32_t)(b - a);
+				for (uint32_t i = threadIdx.x; i < cnt; i += kSuThreads)
+					t.k[d + i] = p[(uint64_t)i * S.stride];
+			}
+			o += len;
+		}
+	}
+	static __device__ __forceinline__ void sort(Lds& t, uint32_t n, uint32_t N)
+	{
+		for (uint32_t i = n + threadIdx.x; i < N; i += kSuThreads)
+			t.k[i] = Key::pad();
+		su_bitonic<Key>(t, N);
+	}
+	static __device__ __forceinline__ void store(const Lds& t, uint32_t n, uint32_t* o)
+	{
+		for (uint32_t i = threadIdx.x; i < n; i += kSuThreads)
+			o[i] = t.k[i];
+	}
+	template <typename Pol>
+	static __device__ __forceinline__ uint64_t unique_lds(uint32_t n, uint64_t seg, const Pol& pol, const Lds& t)
+	{
+		return su_unique_write<Key>(n, seg, pol, [&](uint32_t i) { return t.k[i]; });
+	}
+	template <typename Pol>
+	static __device__ __forceinline__ uint64_t unique_buf(uint32_t n, uint64_t seg, const Pol& pol, const uint32_t* s)
+	{
+		return su_unique_write<Key>(n, seg, pol, [&](uint32_t i) { return s[i]; });
 	}
 };
 

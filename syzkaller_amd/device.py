@@ -311,6 +311,82 @@ class Device:
                                              item_cover.numel(), ctypes.byref(n)))
         return off, item_cover[: n.value]
 
+    # ---------------------------------------------------------------- triage items
+    def triage_items(self, sigs, call_start, call_len, call_prio, call_new, corpus_signal=None, caps=None):
+        """proc.go:232-245 and :107-111 over a batch (syzsig_triage_items_dev):
+        the calls triage flagged in call_new become items, in call order, each
+        with its inputSignal = FromRaw(call's signal, prio) and its newSignal =
+        corpusSignal.Diff(inputSignal) (corpus_signal: a Signal, None = nil).
+        Returns a dict of device tensors: item_call int32[n], item_prio int8[n],
+        input_off int64[n + 1], input_elems int32[] (RPCInput.Signal: item i's
+        elements, ascending, all with item_prio[i]), and item_off int64[n + 1],
+        elems int32[], prios int8[] -- the CSR triage_runs reads.  caps =
+        (items, input entries, new entries) sizes the outputs; None starts from
+        the flagged calls' records being unknown: one call to learn the totals,
+        one to write.  Given caps that are too small raise
+        SyzsigError(SYZSIG_ERANGE) with the three totals in .needed."""
+        self._check_dev(sigs, call_start, call_len, call_prio, call_new)
+        ncalls = call_len.numel()
+        if call_start.numel() != ncalls or call_prio.numel() != ncalls or call_new.numel() != ncalls:
+            raise ValueError("call_start / call_len / call_prio / call_new need one entry per call")
+        cs = corpus_signal.handle if corpus_signal is not None else ctypes.c_void_p(0)
+        n = [ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()]
+
+        def run(ci, cn, cw):
+            r = {"item_call": torch.empty(ci, dtype=torch.int32, device=self.dev),
+                 "item_prio": torch.empty(ci, dtype=torch.int8, device=self.dev),
+                 "input_off": torch.empty(ci + 1, dtype=torch.int64, device=self.dev),
+                 "input_elems": torch.empty(cn, dtype=torch.int32, device=self.dev),
+                 "item_off": torch.empty(ci + 1, dtype=torch.int64, device=self.dev),
+                 "elems": torch.empty(cw, dtype=torch.int32, device=self.dev),
+                 "prios": torch.empty(cw, dtype=torch.int8, device=self.dev)}
+            rc = self.L.syzsig_triage_items_dev(
+                self.eng.h, _p(sigs), sigs.numel(), _p(call_start), _p(call_len), _p(call_prio), ncalls, _p(call_new),
+                cs, _p(r["item_call"]), _p(r["item_prio"]), ci, _p(r["input_off"]), _p(r["input_elems"]), cn,
+                _p(r["item_off"]), _p(r["elems"]), _p(r["prios"]), cw, ctypes.byref(n[0]), ctypes.byref(n[1]),
+                ctypes.byref(n[2]))
+            return rc, r
+
+        rc, r = run(*(caps if caps is not None else (0, 0, 0)))
+        if caps is None and rc == _lib.SYZSIG_ERANGE and n[0].value:
+            rc, r = run(n[0].value, n[1].value, n[2].value)
+        try:
+            check(rc)
+        except _lib.SyzsigError as e:
+            e.needed = tuple(int(x.value) for x in n)
+            raise
+        ni, nin, nnew = (int(x.value) for x in n)
+        return {"item_call": r["item_call"][:ni], "item_prio": r["item_prio"][:ni], "input_off": r["input_off"][:ni + 1],
+                "input_elems": r["input_elems"][:nin], "item_off": r["item_off"][:ni + 1], "elems": r["elems"][:nnew],
+                "prios": r["prios"][:nnew]}
+
+    def triage_items_stats(self):
+        """(items, items past SYZSIG_ITEMS_TILE, rank-merge passes, corpusSignal
+        probes) of the last triage_items call (syzsig_triage_items_stats)."""
+        out = (ctypes.c_uint64 * 4)()
+        check(self.L.syzsig_triage_items_stats(self.eng.h, out))
+        return tuple(int(x) for x in out)
+
+    def corpus_add_inputs(self, input_off, input_elems, item_prio, corpus_signal, max_signal, item_keep=None):
+        """addInputToCorpus (fuzzer.go:446-460) over the items triageInput kept
+        (syzsig_corpus_add_inputs_dev): every item with item_keep != 0 (None =
+        all) and a non-empty inputSignal is max-merged into corpus_signal and
+        max_signal (Signal objects; a nil one is allocated when something is
+        merged).  input_off / input_elems / item_prio as triage_items returned them."""
+        self._check_dev(input_off, input_elems, item_prio, item_keep)
+        nitems = item_prio.numel()
+        if input_off.numel() != nitems + 1 or (item_keep is not None and item_keep.numel() != nitems):
+            raise ValueError("input_off needs nitems + 1 entries, item_keep nitems")
+        ch = ctypes.c_void_p(corpus_signal.handle.value or 0)
+        mh = ctypes.c_void_p(max_signal.handle.value or 0)
+        check(self.L.syzsig_corpus_add_inputs_dev(self.eng.h, _p(input_off), _p(input_elems), input_elems.numel(),
+                                                  _p(item_prio), nitems, _p(item_keep), ctypes.byref(ch),
+                                                  ctypes.byref(mh)))
+        if ch.value and corpus_signal.is_nil():
+            corpus_signal._h = ch
+        if mh.value and max_signal.is_nil():
+            max_signal._h = mh
+
     def minimize_pred(self, item_off, elems, prios, item_flags, attempts, run_off, run_sigs, run_prio, run_errno,
                       run_exec):
         """triageInput's minimize predicate (proc.go:141-160) per item; uint8 tensor."""
