@@ -4,7 +4,14 @@ CPU: the readOutCoverage restatement against the REFERENCE executor's own
 regions (oracle/_ref/ref_harness, container only) and the committed fixture.
 GPU: k_ingest_exec_output bit-exact against the fixture (well-formed regions
 written by the reference executor plus one corrupted region per ipc.go error
-branch), then ingest -> checkNewSignal end to end against the oracle."""
+branch), then ingest -> checkNewSignal end to end against the oracle.
+
+The regions of tests/ingest_cases.py (written by hand: the accepting and the
+rejecting side of every length check, programs of 256 calls and more, 600
+programs over three workgroups) are checked on the CPU against their
+hand-stated status and on the GPU against the restatement, array by array."""
+import ctypes
+import functools
 import os
 
 import numpy as np
@@ -12,6 +19,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests import ingest_cases as IC
 from tests.conftest import GOLDEN
 
 FIX = os.path.join(GOLDEN, "ingest", "exec_regions.npz")
@@ -202,3 +210,153 @@ def test_bench_frame_regions_parse_back():
             assert err == (0 if (prio[c] >> 1) & 1 else 22) and sl == cnt[c]
             reg = out[poff[p]:poff[p + 1]]
             np.testing.assert_array_equal(reg[so:so + sl], sigs[cs[c]:cs[c] + cnt[c]])
+
+
+# ---- regions written by hand (tests/ingest_cases.py) ----
+SETS = {"boundaries": IC.boundaries, "long": IC.long_programs, "batch": IC.batch}
+
+
+@functools.lru_cache(maxsize=None)
+def expected(which, with_call_num=True):
+    """The restatement's result for a set of hand regions, computed once: the
+    inputs and every output array of the kernel, the cover ranges included."""
+    regions = SETS[which]()
+    regs, ncalls, call_any, nums = IC.arrays(regions, with_call_num)
+    out, po, pc, cs, cl, cp, ce, st = O.ingest_batch(regs, ncalls, call_any, nums)
+    cov_s, cov_l = cs.copy(), np.zeros(cl.size, np.uint32)
+    for p, reg in enumerate(regs):
+        c0 = int(pc[p])
+        cov_s[c0:int(pc[p + 1])] = po[p]
+        if st[p] != 0:
+            continue
+        _, info = O.read_out_coverage(reg, int(ncalls[p]), None if nums is None else nums[c0:int(pc[p + 1])])
+        for i, inf in enumerate(info):
+            if inf is not None:
+                cov_s[c0 + i], cov_l[c0 + i] = int(po[p]) + inf[3], inf[4]
+    r = dict(out=out, prog_off=po, prog_call=pc, call_any=call_any, call_num=nums, call_start=cs, call_len=cl,
+             call_prio=cp, call_errno=ce, prog_status=st, cover_start=cov_s, cover_len=cov_l)
+    for v in r.values():
+        if v is not None:
+            v.setflags(write=False)
+    return r
+
+
+@pytest.mark.parametrize("which", ["boundaries", "long"])
+def test_hand_status_is_the_restatements(which):
+    for r in SETS[which]():
+        words = np.array(r.words, np.uint32)
+        st, info = O.read_out_coverage(words, r.ncalls, IC.call_nums(r.ncalls))
+        assert st == r.status, r.name
+        assert O.read_out_coverage(words, r.ncalls)[0] == r.status_nonum, r.name
+        assert len(info) == r.ncalls
+
+
+def test_hand_regions_reach_what_they_are_for():
+    by = {r.name: r for r in IC.boundaries() + IC.long_programs()}
+    assert len(by) == len(IC.boundaries()) + len(IC.long_programs())
+    assert {r.status for r in IC.boundaries()} == set(range(10))  # every ipc.go branch, and success
+    # the accepted region and its rejected neighbour differ by one word or by one in one size field
+    for ok, bad in [("hdr7", "hdr6"), ("nsig_exact", "nsig_plus1"), ("ncover_exact", "ncover_plus1"),
+                    ("comp_type7", "comp_type8"), ("comp8_4left", "comp8_3left"), ("comp4_2left", "comp4_1left"),
+                    ("idx_last", "idx_ncalls")]:
+        a, b = by[ok], by[bad]
+        assert a.status == 0 != b.status and a.ncalls == b.ncalls
+        if len(a.words) == len(b.words):
+            d = [(x, y) for x, y in zip(a.words, b.words) if x != y]
+            assert len(d) == 1 and d[0][1] == d[0][0] + 1, (ok, bad)
+        else:
+            assert len(a.words) == len(b.words) + 1 and a.words[:len(b.words)] == b.words, (ok, bad)
+    # long programs: 256 calls fit the LDS bitmap exactly, 257 and 300 pass it
+    assert {r.ncalls for r in IC.long_programs()} == {IC.SEEN_CALLS, IC.SEEN_CALLS + 1, 300}
+    for nc in (256, 257, 300):
+        st, info = O.read_out_coverage(by[f"long{nc}"].words, nc, IC.call_nums(nc))
+        have = [i is not None for i in info]
+        assert st == 0 and have[255] and have[nc - 1] and not have[254] and not have[3]
+        assert by[f"long{nc}"].words[0] == sum(have)  # ncmd: one record per call that has one
+    st, info = O.read_out_coverage(by["long300"].words, 300, IC.call_nums(300))
+    assert info[256] is not None and info[258] is None and info[270] is None and info[257] is not None
+    # the late failures come after records for calls of 256 and up were accepted
+    for name in ("long300_fails_late", "long300_fails_short", "long257_fails_signal", "long300_double256",
+                 "long257_double256_empty"):
+        st, info = O.read_out_coverage(by[name].words, by[name].ncalls, IC.call_nums(by[name].ncalls))
+        assert st != 0 and any(i is not None for i in info[IC.SEEN_CALLS:]), name
+    # the batch: three workgroups, long programs and every status in each, neighbours of unlike outcome
+    b = IC.batch()
+    assert len(b) == IC.NPROG == 600 and -(-len(b) // IC.THREADS) == 3
+    assert sum(r.ncalls == 2 for r in b) > len(b) * 3 // 4
+    for g in range(3):
+        grp = b[g * IC.THREADS:(g + 1) * IC.THREADS]
+        assert any(r.ncalls > IC.SEEN_CALLS and r.status == 0 for r in grp)
+        assert any(r.ncalls > IC.SEEN_CALLS and r.status != 0 for r in grp)
+        assert g == 2 or any(r.ncalls > IC.SEEN_CALLS for r in grp[64:])  # past the first wave of a full group
+    assert {r.name for r in b} >= set(by)
+    short = [r for r in b if r.name.startswith("short")]
+    assert all((r.status == 0) == (int(r.name[5:]) % 2 == 0) for r in short)
+    for which in SETS:
+        e = expected(which)
+        np.testing.assert_array_equal(e["prog_status"], [r.status for r in SETS[which]()])
+        np.testing.assert_array_equal(expected(which, False)["prog_status"], [r.status_nonum for r in SETS[which]()])
+        assert not (e["call_len"] == IC.NIL_LEN).any()
+        failed = np.repeat(e["prog_status"] != 0, np.diff(e["prog_call"].astype(np.int64)))
+        assert (e["call_len"][failed] == 0).all() and (e["call_errno"][failed] == -1).all()
+        assert 0 < (e["call_len"] > 0).sum() and 0 < (e["cover_len"] > 0).sum()
+
+
+FILL = 0xAA
+
+
+def raw_ingest(gpu, e, want_cover):
+    """syzsig_ingest_exec_output_dev on call outputs pre-filled with 0xAA"""
+    t = lambda a, dt: torch.from_numpy(a.view(dt).copy()).to(gpu.dev)  # noqa: E731
+    from syzkaller_amd.device import _p
+
+    ncalls, nprog = e["call_any"].size, e["prog_status"].size
+    fill = lambda n, dt: torch.full((n * np.dtype(dt).itemsize,), FILL, dtype=torch.uint8, device=gpu.dev)  # noqa: E731
+    o = {"call_start": fill(ncalls, np.uint64), "call_len": fill(ncalls, np.uint32),
+         "call_prio": fill(ncalls, np.uint8), "call_errno": fill(ncalls, np.int32),
+         "prog_status": fill(nprog, np.int32)}
+    if want_cover:
+        o["cover_start"], o["cover_len"] = fill(ncalls, np.uint64), fill(ncalls, np.uint32)
+    out, po, pc = t(e["out"], np.int32), t(e["prog_off"], np.int64), t(e["prog_call"], np.int32)
+    any_, num = t(e["call_any"], np.uint8), None if e["call_num"] is None else t(e["call_num"], np.int32)
+    nf = ctypes.c_uint64()
+    rc = gpu.L.syzsig_ingest_exec_output_dev(
+        gpu.eng.h, _p(out), out.numel(), _p(po), nprog, _p(pc), ncalls, _p(num), _p(any_), _p(o["call_start"]),
+        _p(o["call_len"]), _p(o["call_prio"]), _p(o["call_errno"]), _p(o.get("cover_start")),
+        _p(o.get("cover_len")), _p(o["prog_status"]), ctypes.byref(nf))
+    assert rc == 0
+    dts = dict(call_start=np.uint64, call_len=np.uint32, call_prio=np.uint8, call_errno=np.int32,
+               prog_status=np.int32, cover_start=np.uint64, cover_len=np.uint32)
+    return {k: v.cpu().numpy().view(dts[k]) for k, v in o.items()}, int(nf.value)
+
+
+def check_ingest(gpu, which, want_cover, with_call_num=True):
+    e = expected(which, with_call_num)
+    got, n_failed = raw_ingest(gpu, e, want_cover)
+    assert not (got["call_len"] == IC.NIL_LEN).any()  # no "Signal == nil" sentinel left behind
+    assert set(got) == {"call_start", "call_len", "call_prio", "call_errno", "prog_status"} | (
+        {"cover_start", "cover_len"} if want_cover else set())
+    for k, v in got.items():
+        np.testing.assert_array_equal(v, e[k], err_msg=k)
+    assert n_failed == int((e["prog_status"] != 0).sum()) > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("want_cover", [False, True])
+@pytest.mark.parametrize("which", ["boundaries", "long", "batch"])
+def test_ingest_hand_regions(gpu, which, want_cover):
+    check_ingest(gpu, which, want_cover)
+
+
+@pytest.mark.gpu
+def test_ingest_hand_regions_without_call_num(gpu):
+    check_ingest(gpu, "batch", True, with_call_num=False)
+    e = expected("batch", False)
+    assert (e["prog_status"] != expected("batch")["prog_status"]).any()  # the callNum region now passes
+    # and through the wrapper, which allocates the outputs itself
+    _, r = _dev_ingest(gpu, e["out"].copy(), e["prog_off"].copy(), e["prog_call"].copy(), e["call_any"].copy(), None,
+                       want_cover=True)
+    for k, dt in dict(call_start=np.uint64, call_len=np.uint32, call_prio=np.uint8, call_errno=np.int32,
+                      prog_status=np.int32, cover_start=np.uint64, cover_len=np.uint32).items():
+        np.testing.assert_array_equal(_np(r[k], dt), e[k], err_msg=k)
+    assert r["n_failed"] == int((e["prog_status"] != 0).sum())
