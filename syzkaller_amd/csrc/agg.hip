@@ -42,12 +42,16 @@
 //       elements are written out compactly.  A partition with more distinct
 //       elements than kAggLimit is flagged and redone by k_agg_global (the same
 //       aggregation in an HBM table).
-//   k_agg_finalize  one workgroup per partition's distinct list: probe/insert
+//   k_agg_finalize_x  one workgroup per partition's distinct list: probe/insert
 //       maxSignal, emit the new (call, elem) pairs and call flags, write
 //       M_final, merge newSignal.  maxSignal's home bucket is the top bits of
 //       the same h (internal.h home_bucket), so one partition's probes stay in
-//       one contiguous slice of the table.  Capacity is reserved before it
-//       from the exact distinct count, so nothing is ever retried.
+//       one contiguous slice of the table, which the workgroup owns for the
+//       launch: plain stores, no global atomics.  What leaves its slice goes
+//       to k_fin_deferred; k_agg_finalize is the same decision with global
+//       atomics, for the HBM fallback's lists and for tables with fewer
+//       buckets than partitions.  Capacity is reserved before any of them,
+//       so nothing is ever retried.
 //   k_pairs_mark (optional) per-record new bits from the pairs.
 #include <algorithm>
 #include <utility>
@@ -1465,7 +1469,37 @@ static void launch_agg(const syzsig_ctx* ctx, uint64_t extent, uint32_t P, hipSt
 // ---- fallback: partitions whose distinct elements overflow the LDS table are
 // aggregated in one HBM hash table keyed by h (gkeys[C] + gfl[4][C + 1], C a
 // power of two; slot C is h = 0xFFFFFFFF).  Partitions hold disjoint
-// elements, so one table serves all of them.  One wave per (partition, group).
+// elements, so one table serves all of them.
+// One record of element hash h at `level` with run serial `serial` into the
+// table: find or insert h (linear probing, a CAS on first sight), then the
+// level's first by atomicMin.  bad counts a probe sequence that ran through
+// the whole table (the host reports it as an internal error).
+__device__ __forceinline__ void hbm_absorb(uint32_t* gkeys, uint32_t* gfl, uint64_t C, uint32_t h, uint32_t level,
+                                           uint32_t serial, uint64_t& bad)
+{
+	uint64_t i = C;
+	if (h != kAggEmpty) {
+		i = fmix32(h ^ 0x632BE5ABu) & (C - 1);
+		for (uint64_t step = 0;; step++) {
+			uint32_t key = gkeys[i];
+			if (key == kAggEmpty) {
+				key = atomicCAS(&gkeys[i], kAggEmpty, h);
+				if (key == kAggEmpty)
+					break;
+			}
+			if (key == h)
+				break;
+			i = (i + 1) & (C - 1);
+			if (step >= C) {
+				bad++;
+				return;
+			}
+		}
+	}
+	atomicMin(&gfl[(uint64_t)level * (C + 1) + i], serial);
+}
+
+// k_agg_global: counted cells, one wave per (partition, group of cells).
 __global__ __launch_bounds__(256) void k_agg_global(const uint32_t* __restrict__ recs,
                                                     const uint64_t* __restrict__ rec_base,
                                                     const uint32_t* __restrict__ offsT, uint64_t nchunks, AggGeom g,
@@ -1486,28 +1520,7 @@ __global__ __launch_bounds__(256) void k_agg_global(const uint32_t* __restrict__
 			const uint32_t r = pr[j];
 			const uint32_t k = cg.serial(j, r, g), l = g.level(r);
 			const uint32_t h = (p << g.rbits()) | g.resid(r);
-			uint64_t i = C;
-			if (h != kAggEmpty) {
-				i = fmix32(h ^ 0x632BE5ABu) & (C - 1);
-				for (uint64_t step = 0;; step++) {
-					uint32_t key = gkeys[i];
-					if (key == kAggEmpty) {
-						key = atomicCAS(&gkeys[i], kAggEmpty, h);
-						if (key == kAggEmpty)
-							break;
-					}
-					if (key == h)
-						break;
-					i = (i + 1) & (C - 1);
-					if (step >= C) {
-						bad++;
-						i = ~0ull;
-						break;
-					}
-				}
-			}
-			if (i != ~0ull)
-				atomicMin(&gfl[(uint64_t)l * (C + 1) + i], k);
+			hbm_absorb(gkeys, gfl, C, h, l, k, bad);
 		}
 	}
 	block_count(err, bad);
@@ -1546,11 +1559,218 @@ __global__ __launch_bounds__(256) void k_agg_global_compact(const uint32_t* __re
 }
 
 // ---------------------------------------------------------------- finalize
+// checkNewSignal's decision for one distinct element e with level firsts f4,
+// in pieces that the three finalize codes compose:
+//   fin_top      the top level present; M_final[e] can only become P = lm.val[top]
+//   (the slot)   e's maxSignal slot, found or inserted -- the one step that
+//                differs: global atomics (fin_commit_atomic, for k_agg_finalize
+//                and k_fin_deferred) or the block's own slice (k_agg_finalize_x)
+//   fin_raises   M0[e] from the slot's word; whether P raises it; the counts
+//   (newSignal)  merge (e, P), by the same means as the slot
+//   fin_emit     the staircase above M0[e] (stair_walk): call_new and the pairs
+// Arguments of the finalize kernels (fin_tables and fin_args fill them).
+struct FinArgs {
+	LevelMap lm;
+	uint64_t c0;
+	uint64_t* slots;  // maxSignal
+	uint64_t bmask;
+	uint64_t* ns_slots;  // newSignal
+	uint64_t ns_bmask;
+	uint8_t* call_new;
+	uint64_t* pairs;
+	unsigned long long* npairs;
+	unsigned long long* ctr;
+	// the slice-exclusive finalize only: log2 of a partition's slice in buckets,
+	// the deferred lists, SYZSIG_DEBUG_FIN_DEFER
+	uint32_t ms_shift, ns_shift;
+	uint32_t* def_e;
+	uint4* def_f;
+	unsigned long long* def_cnt;
+	uint64_t* def_ns;
+	unsigned long long* def_ns_cnt;
+	uint32_t dbg;
+	// a one-sync run: its void flag, and the counter of overflowed partitions
+	// with the gate past which nothing is committed
+	const uint32_t* spill;
+	const unsigned long long* ovf_gate;
+	uint32_t gate_max;
+};
+
+// What a finalize kernel counts, and its epilogue.
+struct FinCounts {
+	uint64_t inserted = 0, changed = 0, ns_ins = 0, ovf = 0;
+	// every thread of the block (kOvf = false: the kernel cannot overflow a table)
+	template <bool kOvf = true>
+	__device__ __forceinline__ void report(unsigned long long* ctr) const
+	{
+		block_count(&ctr[kCntInserted], inserted);
+		block_count(&ctr[kCntChanged], changed);
+		block_count(&ctr[kCntAux], ns_ins);
+		if (kOvf)
+			block_count(&ctr[kCntOverflow], ovf);
+	}
+};
+
+// the top level present among the run's lm.n, or -1 (none, or !valid)
+__device__ __forceinline__ int fin_top(uint4 f4, const LevelMap& lm, bool valid)
+{
+	const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
+	int top = -1;
+#pragma unroll
+	for (int l = 0; l < 4; l++)
+		if (valid && l < (int)lm.n && f[l] != kAggNone)
+			top = l;
+	return top;
+}
+
+// p0 = M0[e] from the word `old` of e's maxSignal slot (0: inserted or claimed
+// just now; an "absent" marker is not live).  True when P raises it, counted.
+__device__ __forceinline__ bool fin_raises(uint64_t old, int8_t P, FinCounts& n, int& p0)
+{
+	const bool present = slot_live(old);
+	p0 = present ? (int)slot_prio(old) : -1000;
+	if ((int)P <= p0)
+		return false;
+	n.inserted += !present;  // fresh, or an "absent" marker going live
+	n.changed++;
+	return true;
+}
+
+// The staircase of an element's level firsts: from level `top` down, the
+// first records of strictly rising level -- each earlier than every record of
+// a higher level -- as on(level, first).  cut(level) ends the walk there.
+template <typename Cut, typename On>
+__device__ __forceinline__ void stair_walk(uint4 f4, int top, Cut cut, On on)
+{
+	const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
+	uint32_t mk = kAggNone;
+#pragma unroll
+	for (int l = 3; l >= 0; l--) {
+		if (l > top || f[l] == kAggNone)
+			continue;
+		if (cut(l))
+			break;
+		if (f[l] < mk) {
+			mk = f[l];
+			on(l, f[l]);
+		}
+	}
+}
+
+// The staircase above M0[e] = p0 holds e's new records: their calls are
+// flagged and put(call << 32 | e) takes the pairs.
+template <typename Put>
+__device__ __forceinline__ void fin_emit(const FinArgs& a, uint32_t e, uint4 f4, int top, int p0, Put put)
+{
+	stair_walk(f4, top, [&](int l) { return (int)a.lm.val[l] <= p0; },
+	           [&](int, uint32_t first) {
+		           const uint64_t c = a.c0 + first;
+		           a.call_new[c] = 1;
+		           put((c << 32) | e);
+	           });
+}
+
+// The decision up to the staircase, with the global-atomic table code: one
+// probe sequence inserts M_final = P if e is absent, else reads M0[e]; then
+// M_final is stored and newSignal merged.  bm, bn: the home buckets of e in
+// the two tables when the caller loaded them ahead.  True (p0 set) when e's
+// staircase is to be emitted.
+__device__ __forceinline__ bool fin_commit_atomic(const FinArgs& a, uint32_t e, int8_t P, FinCounts& n, int& p0,
+                                                  const Bucket* bm = nullptr, const Bucket* bn = nullptr)
+{
+	const uint64_t word = make_slot(e, P), max_probe = max_probe_for(a.bmask);
+	uint64_t old = 0;
+	const int64_t idx = bm ? tbl_find_or_insert_from(a.slots, a.bmask, e, word, old, max_probe, *bm)
+	                       : tbl_find_or_insert(a.slots, a.bmask, e, word, old, max_probe);
+	if (idx < 0) {
+		n.ovf++;
+		return false;
+	}
+	if (!fin_raises(old, P, n, p0))  // (old == 0: inserted just now)
+		return false;
+	if (old != 0)
+		a.slots[idx] = word;  // one entry per element: no other writer
+	const int rr = bn ? tbl_merge_from(a.ns_slots, a.ns_bmask, e, P, *bn) : tbl_merge(a.ns_slots, a.ns_bmask, e, P);
+	n.ns_ins += rr == 1;
+	n.ovf += rr < 0;
+	return true;
+}
+
+// A block's pairs, gathered in LDS and appended to pairs[] with one global
+// atomic per flush (a pair that finds the buffer full is appended directly).
+template <uint32_t kCap>
+struct PairBuf {
+	uint64_t buf[kCap];
+	uint32_t n;
+	unsigned long long base;
+	__device__ __forceinline__ void reset()  // (a barrier must follow)
+	{
+		if (threadIdx.x == 0)
+			n = 0;
+	}
+	__device__ __forceinline__ void emit(uint64_t v, uint64_t* pairs, unsigned long long* npairs)
+	{
+		const uint32_t k = atomicAdd(&n, 1u);
+		if (k < kCap)
+			buf[k] = v;
+		else
+			pairs[atomicAdd(npairs, 1ull)] = v;
+	}
+	// every thread of the block, after a pass of emits
+	__device__ __forceinline__ void flush_if_half(uint64_t* pairs, unsigned long long* npairs)
+	{
+		__syncthreads();
+		const uint32_t nb = n;
+		if (nb > kCap / 2)
+			flush(nb, pairs, npairs);
+	}
+	__device__ __forceinline__ void flush_all(uint64_t* pairs, unsigned long long* npairs)
+	{
+		__syncthreads();
+		const uint32_t nb = n;
+		if (nb)
+			flush(nb, pairs, npairs);
+	}
+	__device__ __forceinline__ void flush(uint32_t nb, uint64_t* pairs, unsigned long long* npairs)
+	{
+		nb = min(nb, kCap);
+		if (threadIdx.x == 0)
+			base = atomicAdd(npairs, (unsigned long long)nb);
+		__syncthreads();
+		for (uint32_t t = threadIdx.x; t < nb; t += blockDim.x)
+			pairs[base + t] = buf[t];
+		__syncthreads();
+		reset();
+		__syncthreads();
+	}
+};
+
+// A thread's kIlp elements of one pass (from entry i0) over region r of n
+// entries, for a block of kThreads: the element, its level firsts and top level.
+template <uint32_t kIlp, uint32_t kThreads>
+struct FinElems {
+	uint32_t e[kIlp];
+	uint4 f4[kIlp];
+	int top[kIlp];  // -1: nothing to decide
+	__device__ __forceinline__ void load(const uint32_t* __restrict__ dist_e, const uint4* __restrict__ dist_f,
+	                                     uint32_t r, uint32_t n, uint32_t i0, const LevelMap& lm)
+	{
+#pragma unroll
+		for (uint32_t k = 0; k < kIlp; k++) {
+			const uint32_t i = i0 + k * kThreads + threadIdx.x;
+			const uint64_t o = (uint64_t)r * kAggRegion + min(i, n - 1);
+			e[k] = dist_e[o];
+			f4[k] = dist_f[o];
+			top[k] = fin_top(f4[k], lm, i < n);
+		}
+	}
+};
+
+// ---- the finalize with device-scope atomics: any regions, any table sizes
+// (the HBM fallback's lists; tables with fewer buckets than partitions) ----
 // One workgroup per region r = dist_*[r * kAggRegion, + cnt[r]): a partition's
 // distinct elements, whose maxSignal/newSignal home buckets share one slice of
 // each table (the same top bits of h), so a block's probes stay in one slice.
-// A block gathers its pairs in LDS and appends them with one global atomic
-// per flush (a pair that finds the buffer full is appended directly).
 // Each thread takes kFinIlp elements per pass and issues the loads of all their
 // home buckets (maxSignal and newSignal) before walking any of them: the
 // kernel is bound by the latency of these dependent random reads, not by
@@ -1560,121 +1780,37 @@ constexpr uint32_t kFinThreads = 256, kFinBuf = 4 * kFinThreads * 2, kFinIlp = 2
 __global__ __launch_bounds__(kFinThreads) void k_agg_finalize(const uint32_t* __restrict__ dist_e,
                                                               const uint4* __restrict__ dist_f,
                                                               const uint32_t* __restrict__ cnt, uint32_t nregions,
-                                                              LevelMap lm, uint64_t c0, uint64_t* slots,
-                                                              uint64_t bmask, uint64_t* ns_slots, uint64_t ns_bmask,
-                                                              uint8_t* call_new, uint64_t* pairs,
-                                                              unsigned long long* npairs, unsigned long long* ctr)
+                                                              FinArgs a)
 {
-	__shared__ uint64_t buf[kFinBuf];
-	__shared__ uint32_t s_n;
-	__shared__ unsigned long long s_base;
-	const uint64_t max_probe = max_probe_for(bmask);
-	uint64_t inserted = 0, changed = 0, ns_ins = 0, ovf = 0;
-	if (threadIdx.x == 0)
-		s_n = 0;
+	__shared__ PairBuf<kFinBuf> pb;
+	FinCounts n;
+	const auto put = [&](uint64_t v) { pb.emit(v, a.pairs, a.npairs); };
+	pb.reset();
 	__syncthreads();
-	auto flush = [&](uint32_t nb) {  // every thread; nb = s_n read after a barrier
-		nb = min(nb, kFinBuf);
-		if (threadIdx.x == 0)
-			s_base = atomicAdd(npairs, (unsigned long long)nb);
-		__syncthreads();
-		for (uint32_t t = threadIdx.x; t < nb; t += blockDim.x)
-			pairs[s_base + t] = buf[t];
-		__syncthreads();
-		if (threadIdx.x == 0)
-			s_n = 0;
-		__syncthreads();
-	};
-	auto emit = [&](uint64_t v) {
-		const uint32_t k = atomicAdd(&s_n, 1u);
-		if (k < kFinBuf)
-			buf[k] = v;
-		else
-			pairs[atomicAdd(npairs, 1ull)] = v;
-	};
 	for (uint32_t r = blockIdx.x; r < nregions; r += gridDim.x) {
-		const uint32_t n = cnt[r] == kAggOverflow ? 0 : cnt[r];
-		for (uint32_t i0 = 0; i0 < n; i0 += kFinIlp * kFinThreads) {
-			uint32_t e[kFinIlp];
-			uint4 f4[kFinIlp];
-			int top[kFinIlp];
-#pragma unroll
-			for (uint32_t k = 0; k < kFinIlp; k++) {
-				const uint32_t i = i0 + k * kFinThreads + threadIdx.x;
-				const uint64_t o = (uint64_t)r * kAggRegion + min(i, n - 1);
-				e[k] = dist_e[o];
-				f4[k] = dist_f[o];
-				top[k] = -1;
-				const uint32_t f[4] = {f4[k].x, f4[k].y, f4[k].z, f4[k].w};
-#pragma unroll
-				for (int l = 0; l < 4; l++)
-					if (i < n && l < (int)lm.n && f[l] != kAggNone)
-						top[k] = l;
-			}
+		const uint32_t nr = cnt[r] == kAggOverflow ? 0 : cnt[r];
+		for (uint32_t i0 = 0; i0 < nr; i0 += kFinIlp * kFinThreads) {
+			FinElems<kFinIlp, kFinThreads> t;
+			t.load(dist_e, dist_f, r, nr, i0, a.lm);
 			Bucket bm[kFinIlp], bn[kFinIlp];
 #pragma unroll
 			for (uint32_t k = 0; k < kFinIlp; k++) {
-				if (top[k] >= 0) {
-					bm[k] = load_bucket(slots + (home_bucket(e[k], bmask) << kBucketShift));
-					if (ns_slots)
-						bn[k] = load_bucket(ns_slots + (home_bucket(e[k], ns_bmask) << kBucketShift));
+				if (t.top[k] >= 0) {
+					bm[k] = load_bucket(a.slots + (home_bucket(t.e[k], a.bmask) << kBucketShift));
+					bn[k] = load_bucket(a.ns_slots + (home_bucket(t.e[k], a.ns_bmask) << kBucketShift));
 				}
 			}
 #pragma unroll
 			for (uint32_t k = 0; k < kFinIlp; k++) {
-				if (top[k] < 0)
-					continue;
-				const uint32_t f[4] = {f4[k].x, f4[k].y, f4[k].z, f4[k].w};
-				// one probe sequence: insert M_final if absent, else read M0
-				const int8_t P = lm.val[top[k]];
-				const uint64_t word = make_slot(e[k], P);
-				uint64_t old = 0;
-				const int64_t idx = tbl_find_or_insert_from(slots, bmask, e[k], word, old, max_probe, bm[k]);
-				if (idx < 0) {
-					ovf++;
-					continue;
-				}
-				const bool present = slot_live(old);  // (old == 0: inserted just now)
-				const int p0 = present ? (int)slot_prio(old) : -1000;
-				if ((int)P <= p0)
-					continue;
-				if (old != 0)
-					slots[idx] = word;  // one entry per element: no other writer
-				inserted += !present;   // fresh, or an "absent" marker going live
-				changed++;
-				const int rr = tbl_merge_from(ns_slots, ns_bmask, e[k], P, bn[k]);
-				ns_ins += rr == 1;
-				ovf += rr < 0;
-				// the staircase: first records of strictly rising level above M0[e]
-				uint32_t mk = kAggNone;
-#pragma unroll
-				for (int l = 3; l >= 0; l--) {
-					if (l > top[k] || f[l] == kAggNone)
-						continue;
-					if ((int)lm.val[l] <= p0)
-						break;
-					if (f[l] < mk) {
-						mk = f[l];
-						const uint64_t c = c0 + f[l];
-						call_new[c] = 1;
-						emit((c << 32) | e[k]);
-					}
-				}
+				int p0 = 0;
+				if (t.top[k] >= 0 && fin_commit_atomic(a, t.e[k], a.lm.val[t.top[k]], n, p0, &bm[k], &bn[k]))
+					fin_emit(a, t.e[k], t.f4[k], t.top[k], p0, put);
 			}
-			__syncthreads();
-			const uint32_t nb = s_n;
-			if (nb > kFinBuf / 2)
-				flush(nb);
+			pb.flush_if_half(a.pairs, a.npairs);
 		}
 	}
-	__syncthreads();
-	const uint32_t nb = s_n;
-	if (nb)
-		flush(nb);
-	block_count(&ctr[kCntInserted], inserted);
-	block_count(&ctr[kCntChanged], changed);
-	block_count(&ctr[kCntAux], ns_ins);
-	block_count(&ctr[kCntOverflow], ovf);
+	pb.flush_all(a.pairs, a.npairs);
+	n.report(a.ctr);
 }
 
 // ---- the finalize without device-scope atomics (the fast path) ----
@@ -1747,268 +1883,129 @@ __device__ __forceinline__ int64_t fx_walk(const uint64_t* tab, uint64_t b, uint
 }
 
 template <uint32_t kFxIlp>
-__global__ __launch_bounds__(kFxThreads) void k_agg_finalize_x(
-    const uint32_t* __restrict__ dist_e, const uint4* __restrict__ dist_f, const uint32_t* __restrict__ cnt,
-    uint32_t nregions, LevelMap lm, uint64_t c0, uint64_t* slots, uint64_t bmask, uint32_t ms_shift,
-    uint64_t* ns_slots, uint64_t ns_bmask, uint32_t ns_shift, uint8_t* call_new, uint64_t* pairs,
-    unsigned long long* npairs, unsigned long long* ctr, uint32_t* def_e, uint4* def_f,
-    unsigned long long* def_cnt, uint64_t* def_ns, unsigned long long* def_ns_cnt, uint32_t dbg,
-    const uint32_t* spill, const unsigned long long* ovf_gate, uint32_t gate_max)
+__global__ __launch_bounds__(kFxThreads) void k_agg_finalize_x(const uint32_t* __restrict__ dist_e,
+                                                               const uint4* __restrict__ dist_f,
+                                                               const uint32_t* __restrict__ cnt, uint32_t nregions,
+                                                               FinArgs a)
 {
 	__shared__ uint32_t claim[kFxSet];
-	__shared__ uint64_t buf[kFxBuf];
-	__shared__ uint32_t s_n;
-	__shared__ unsigned long long s_base;
-	if (spill && *spill)
+	__shared__ PairBuf<kFxBuf> pb;
+	if (a.spill && *a.spill)
 		return;  // a cell spilled: nothing is committed, the run is redone
-	if (ovf_gate && *ovf_gate > gate_max)
+	if (a.ovf_gate && *a.ovf_gate > a.gate_max)
 		return;  // the partitions were too few for the run's distinct elements: redone with more
-	uint64_t inserted = 0, changed = 0, ns_ins = 0;
-	auto flush = [&](uint32_t nb) {  // every thread; nb = s_n read after a barrier
-		nb = min(nb, kFxBuf);
-		if (threadIdx.x == 0)
-			s_base = atomicAdd(npairs, (unsigned long long)nb);
-		__syncthreads();
-		for (uint32_t t = threadIdx.x; t < nb; t += blockDim.x)
-			pairs[s_base + t] = buf[t];
-		__syncthreads();
-		if (threadIdx.x == 0)
-			s_n = 0;
-		__syncthreads();
-	};
-	auto emit = [&](uint64_t v) {
-		const uint32_t k = atomicAdd(&s_n, 1u);
-		if (k < kFxBuf)
-			buf[k] = v;
-		else
-			pairs[atomicAdd(npairs, 1ull)] = v;
-	};
+	FinCounts n;
+	const auto put = [&](uint64_t v) { pb.emit(v, a.pairs, a.npairs); };
 	for (uint32_t r = blockIdx.x; r < nregions; r += gridDim.x) {
 		for (uint32_t i = threadIdx.x; i < kFxSet; i += blockDim.x)
 			claim[i] = 0;
-		if (threadIdx.x == 0)
-			s_n = 0;
+		pb.reset();
 		__syncthreads();
-		const uint64_t ms0 = (uint64_t)r << ms_shift, ms1 = (uint64_t)(r + 1) << ms_shift;
-		const uint64_t ns0 = (uint64_t)r << ns_shift, ns1 = (uint64_t)(r + 1) << ns_shift;
-		const uint32_t n = cnt[r];
-		if (n == kAggOverflow)
+		const uint64_t ms0 = (uint64_t)r << a.ms_shift, ms1 = (uint64_t)(r + 1) << a.ms_shift;
+		const uint64_t ns0 = (uint64_t)r << a.ns_shift, ns1 = (uint64_t)(r + 1) << a.ns_shift;
+		const uint32_t nr = cnt[r];
+		if (nr == kAggOverflow)
 			continue;  // past the LDS table: aggregated in HBM and committed after this launch
-		for (uint32_t i0 = 0; i0 < n; i0 += kFxIlp * kFxThreads) {
-			uint32_t e[kFxIlp];
-			uint4 f4[kFxIlp];
-			int top[kFxIlp];
-#pragma unroll
-			for (uint32_t k = 0; k < kFxIlp; k++) {
-				const uint32_t i = i0 + k * kFxThreads + threadIdx.x;
-				const uint64_t o = (uint64_t)r * kAggRegion + min(i, n - 1);
-				e[k] = dist_e[o];
-				f4[k] = dist_f[o];
-				top[k] = -1;
-				const uint32_t f[4] = {f4[k].x, f4[k].y, f4[k].z, f4[k].w};
-#pragma unroll
-				for (int l = 0; l < 4; l++)
-					if (i < n && l < (int)lm.n && f[l] != kAggNone)
-						top[k] = l;
-			}
+		for (uint32_t i0 = 0; i0 < nr; i0 += kFxIlp * kFxThreads) {
+			FinElems<kFxIlp, kFxThreads> t;
+			t.load(dist_e, dist_f, r, nr, i0, a.lm);
 			Bucket bm[kFxIlp], bn[kFxIlp];
 #pragma unroll
 			for (uint32_t k = 0; k < kFxIlp; k++) {
-				if (top[k] >= 0) {
-					bm[k] = load_bucket(slots + (home_bucket(e[k], bmask) << kBucketShift));
-					bn[k] = load_bucket(ns_slots + (home_bucket(e[k], ns_bmask) << kBucketShift));
+				if (t.top[k] >= 0) {
+					bm[k] = load_bucket(a.slots + (home_bucket(t.e[k], a.bmask) << kBucketShift));
+					bn[k] = load_bucket(a.ns_slots + (home_bucket(t.e[k], a.ns_bmask) << kBucketShift));
 				}
 			}
 #pragma unroll
 			for (uint32_t k = 0; k < kFxIlp; k++) {
-				if (top[k] < 0)
+				if (t.top[k] < 0)
 					continue;
-				const uint32_t f[4] = {f4[k].x, f4[k].y, f4[k].z, f4[k].w};
-				const int8_t P = lm.val[top[k]];
-				const uint64_t word = make_slot(e[k], P);
+				const uint32_t e = t.e[k];
+				const int8_t P = a.lm.val[t.top[k]];
+				const uint64_t word = make_slot(e, P);
 				uint64_t old = 0;
 				// (SYZSIG_DEBUG_FIN_DEFER, tests: defer every walk that leaves the home bucket)
-				const uint64_t hm = home_bucket(e[k], bmask), hn = home_bucket(e[k], ns_bmask);
-				const int64_t idx = fx_walk(slots, hm, dbg & SYZSIG_DEBUG_FIN_DEFER ? hm + 1 : ms1,
-				                            ms0 << kBucketShift, e[k], bm[k], claim, 0, old);
+				const uint64_t hm = home_bucket(e, a.bmask), hn = home_bucket(e, a.ns_bmask);
+				const int64_t idx = fx_walk(a.slots, hm, a.dbg & SYZSIG_DEBUG_FIN_DEFER ? hm + 1 : ms1,
+				                            ms0 << kBucketShift, e, bm[k], claim, 0, old);
 				if (idx < 0) {  // the atomic path takes the whole element
-					const uint64_t d = atomicAdd(def_cnt, 1ull);
-					def_e[d] = e[k];
-					def_f[d] = f4[k];
+					const uint64_t d = atomicAdd(a.def_cnt, 1ull);
+					a.def_e[d] = e;
+					a.def_f[d] = t.f4[k];
 					continue;
 				}
-				const bool present = slot_live(old);
-				const int p0 = present ? (int)slot_prio(old) : -1000;
-				if ((int)P <= p0)
+				int p0 = 0;
+				if (!fin_raises(old, P, n, p0))
 					continue;  // (a claimed slot always has P > p0)
-				slots[idx] = word;    // the block's own slice: no other writer
-				inserted += !present; // fresh, or an "absent" marker going live
-				changed++;
+				a.slots[idx] = word;  // the block's own slice: no other writer
 				uint64_t nold = 0;
-				const int64_t nidx = fx_walk(ns_slots, hn, dbg & SYZSIG_DEBUG_FIN_DEFER ? hn + 1 : ns1,
-				                             ns0 << kBucketShift, e[k], bn[k], claim, 1, nold);
+				const int64_t nidx = fx_walk(a.ns_slots, hn, a.dbg & SYZSIG_DEBUG_FIN_DEFER ? hn + 1 : ns1,
+				                             ns0 << kBucketShift, e, bn[k], claim, 1, nold);
 				if (nidx < 0) {
-					def_ns[atomicAdd(def_ns_cnt, 1ull)] = ((uint64_t)e[k] << 32) | prio_biased(P);
+					a.def_ns[atomicAdd(a.def_ns_cnt, 1ull)] = ((uint64_t)e << 32) | prio_biased(P);
 				} else if (nold == 0 || nold < word) {
-					ns_slots[nidx] = word;
-					ns_ins += nold == 0;
+					a.ns_slots[nidx] = word;
+					n.ns_ins += nold == 0;
 				}
-				// the staircase: first records of strictly rising level above M0[e]
-				uint32_t mk = kAggNone;
-#pragma unroll
-				for (int l = 3; l >= 0; l--) {
-					if (l > top[k] || f[l] == kAggNone)
-						continue;
-					if ((int)lm.val[l] <= p0)
-						break;
-					if (f[l] < mk) {
-						mk = f[l];
-						const uint64_t c = c0 + f[l];
-						call_new[c] = 1;
-						emit((c << 32) | e[k]);
-					}
-				}
+				fin_emit(a, e, t.f4[k], t.top[k], p0, put);
 			}
-			__syncthreads();
-			const uint32_t nb = s_n;
-			if (nb > kFxBuf / 2)
-				flush(nb);
+			pb.flush_if_half(a.pairs, a.npairs);
 		}
-		__syncthreads();
-		const uint32_t nb = s_n;
-		if (nb)
-			flush(nb);
+		pb.flush_all(a.pairs, a.npairs);
 	}
-	block_count(&ctr[kCntInserted], inserted);
-	block_count(&ctr[kCntChanged], changed);
-	block_count(&ctr[kCntAux], ns_ins);
+	n.report<false>(a.ctr);
 }
 
 // Deferred elements of k_agg_finalize_x, with the global-atomic table code
 // (launched after it: the slices are free for everyone again).
-__device__ void fin_deferred(const uint32_t* __restrict__ def_e, const uint4* __restrict__ def_f,
-                                                      const unsigned long long* __restrict__ def_cnt, LevelMap lm,
-                                                      uint64_t c0, uint64_t* slots, uint64_t bmask, uint64_t* ns_slots,
-                                                      uint64_t ns_bmask, uint8_t* call_new, uint64_t* pairs,
-                                                      unsigned long long* npairs, unsigned long long* ctr,
-                                                      uint32_t nblocks, uint32_t block)
+__device__ __forceinline__ void fin_deferred(const FinArgs& a, uint32_t nblocks, uint32_t block)
 {
-	const uint64_t n = *def_cnt, max_probe = max_probe_for(bmask);
-	uint64_t inserted = 0, changed = 0, ns_ins = 0, ovf = 0;
-	for (uint64_t i = block * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)nblocks * blockDim.x) {
-		const uint32_t e = def_e[i];
-		const uint4 f4 = def_f[i];
-		const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
-		int top = -1;
-#pragma unroll
-		for (int l = 0; l < 4; l++)
-			if (l < (int)lm.n && f[l] != kAggNone)
-				top = l;
-		if (top < 0)
-			continue;
-		const int8_t P = lm.val[top];
-		const uint64_t word = make_slot(e, P);
-		uint64_t old = 0;
-		const int64_t idx = tbl_find_or_insert(slots, bmask, e, word, old, max_probe);
-		if (idx < 0) {
-			ovf++;
-			continue;
-		}
-		const bool present = slot_live(old);
-		const int p0 = present ? (int)slot_prio(old) : -1000;
-		if ((int)P <= p0)
-			continue;
-		if (old != 0)
-			slots[idx] = word;
-		inserted += !present;
-		changed++;
-		const int rr = tbl_merge(ns_slots, ns_bmask, e, P);
-		ns_ins += rr == 1;
-		ovf += rr < 0;
-		uint32_t mk = kAggNone;
-#pragma unroll
-		for (int l = 3; l >= 0; l--) {
-			if (l > top || f[l] == kAggNone)
-				continue;
-			if ((int)lm.val[l] <= p0)
-				break;
-			if (f[l] < mk) {
-				mk = f[l];
-				const uint64_t c = c0 + f[l];
-				call_new[c] = 1;
-				pairs[atomicAdd(npairs, 1ull)] = (c << 32) | e;
-			}
-		}
+	const uint64_t nd = *a.def_cnt;
+	FinCounts n;
+	for (uint64_t i = block * (uint64_t)blockDim.x + threadIdx.x; i < nd; i += (uint64_t)nblocks * blockDim.x) {
+		const uint32_t e = a.def_e[i];
+		const uint4 f4 = a.def_f[i];
+		const int top = fin_top(f4, a.lm, true);
+		int p0 = 0;
+		if (top >= 0 && fin_commit_atomic(a, e, a.lm.val[top], n, p0))
+			fin_emit(a, e, f4, top, p0, [&](uint64_t v) { a.pairs[atomicAdd(a.npairs, 1ull)] = v; });
 	}
-	block_count(&ctr[kCntInserted], inserted);
-	block_count(&ctr[kCntChanged], changed);
-	block_count(&ctr[kCntAux], ns_ins);
-	block_count(&ctr[kCntOverflow], ovf);
+	n.report(a.ctr);
 }
 
 // Deferred newSignal merges of k_agg_finalize_x: (elem << 32 | prio ^ 0x80).
-__device__ void ns_deferred(const uint64_t* __restrict__ def_ns, const unsigned long long* __restrict__ def_ns_cnt,
-                            uint64_t* ns_slots, uint64_t ns_bmask, unsigned long long* ctr, uint32_t nblocks,
-                            uint32_t block)
+__device__ __forceinline__ void ns_deferred(const FinArgs& a, uint32_t nblocks, uint32_t block)
 {
-	const uint64_t n = *def_ns_cnt;
+	const uint64_t nd = *a.def_ns_cnt;
 	uint64_t ins = 0, ovf = 0;
-	for (uint64_t i = block * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)nblocks * blockDim.x) {
-		const uint64_t v = def_ns[i];
-		const int r = tbl_merge(ns_slots, ns_bmask, (uint32_t)(v >> 32), (int8_t)((uint8_t)v ^ 0x80u));
+	for (uint64_t i = block * (uint64_t)blockDim.x + threadIdx.x; i < nd; i += (uint64_t)nblocks * blockDim.x) {
+		const uint64_t v = a.def_ns[i];
+		const int r = tbl_merge(a.ns_slots, a.ns_bmask, (uint32_t)(v >> 32), (int8_t)((uint8_t)v ^ 0x80u));
 		ins += r == 1;
 		ovf += r < 0;
 	}
-	block_count(&ctr[kCntAux], ins);
-	block_count(&ctr[kCntOverflow], ovf);
+	block_count(&a.ctr[kCntAux], ins);
+	block_count(&a.ctr[kCntOverflow], ovf);
 }
 
 // Both deferred lists in one launch: the first kDeferBlocks blocks take the
 // elements, the rest the newSignal merges (both sides only ever max-merge
 // newSignal with atomics, so they commute).
 constexpr uint32_t kDeferBlocks = 64;
-__global__ __launch_bounds__(256) void k_fin_deferred(const uint32_t* __restrict__ def_e, const uint4* __restrict__ def_f,
-                                                      const unsigned long long* __restrict__ def_cnt, LevelMap lm,
-                                                      uint64_t c0, uint64_t* slots, uint64_t bmask, uint64_t* ns_slots,
-                                                      uint64_t ns_bmask, uint8_t* call_new, uint64_t* pairs,
-                                                      unsigned long long* npairs, unsigned long long* ctr,
-                                                      const uint64_t* __restrict__ def_ns,
-                                                      const unsigned long long* __restrict__ def_ns_cnt)
+__global__ __launch_bounds__(256) void k_fin_deferred(FinArgs a)
 {
 	if (blockIdx.x < kDeferBlocks)
-		fin_deferred(def_e, def_f, def_cnt, lm, c0, slots, bmask, ns_slots, ns_bmask, call_new, pairs, npairs, ctr,
-		             kDeferBlocks, blockIdx.x);
+		fin_deferred(a, kDeferBlocks, blockIdx.x);
 	else
-		ns_deferred(def_ns, def_ns_cnt, ns_slots, ns_bmask, ctr, gridDim.x - kDeferBlocks, blockIdx.x - kDeferBlocks);
+		ns_deferred(a, gridDim.x - kDeferBlocks, blockIdx.x - kDeferBlocks);
 }
 
 // ---------------------------------------------------------------- one-sync run
-// The arguments of the slice-exclusive finalize and its deferred lists
-// (fin_args fills them, fin_launch hands them to the kernels).
 // (Round 3 measured aggregation and finalize in one launch -- the distinct
 // elements kept in registers, the freed LDS as claim set -- at 1.18 ms against
 // 0.64 + 0.27 for the two launches at C2, and removed it: one 1024-thread
 // workgroup per CU held the LDS through its random probes.)
-struct FinArgs {
-	LevelMap lm;
-	uint64_t c0;
-	uint64_t* slots;
-	uint64_t bmask;
-	uint32_t ms_shift;
-	uint64_t* ns_slots;
-	uint64_t ns_bmask;
-	uint32_t ns_shift;
-	uint8_t* call_new;
-	uint64_t* pairs;
-	unsigned long long* npairs;
-	unsigned long long* ctr;
-	uint32_t* def_e;
-	uint4* def_f;
-	unsigned long long* def_cnt;
-	uint64_t* def_ns;
-	unsigned long long* def_ns_cnt;
-	uint32_t dbg;
-};
 
 // Fallback of the one-sync run: the records of the partitions that overflowed
 // the LDS table, aggregated in one HBM table keyed by h (as k_agg_global) from
@@ -2033,28 +2030,7 @@ __global__ __launch_bounds__(256) void k_agg_global_cap(const uint32_t* __restri
 			const uint32_t r = pr[j];
 			const uint32_t k = ((uint32_t)c << g.cbits()) | g.local(r), l = g.level(r);
 			const uint32_t h = (p << g.rbits()) | g.resid(r);
-			uint64_t i = C;
-			if (h != kAggEmpty) {
-				i = fmix32(h ^ 0x632BE5ABu) & (C - 1);
-				for (uint64_t step = 0;; step++) {
-					uint32_t key = gkeys[i];
-					if (key == kAggEmpty) {
-						key = atomicCAS(&gkeys[i], kAggEmpty, h);
-						if (key == kAggEmpty)
-							break;
-					}
-					if (key == h)
-						break;
-					i = (i + 1) & (C - 1);
-					if (step >= C) {
-						bad++;
-						i = ~0ull;
-						break;
-					}
-				}
-			}
-			if (i != ~0ull)
-				atomicMin(&gfl[(uint64_t)l * (C + 1) + i], k);
+			hbm_absorb(gkeys, gfl, C, h, l, k, bad);
 		}
 	}
 	block_count(err, bad);
@@ -2321,6 +2297,25 @@ static int cap_scatter_agg(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, 
 // kCapSdMax), or a partition overflowed the LDS table (its HBM fallback reads
 // counted cells).
 constexpr float kCapSdMax = 24.0f;
+static void cap_slack_after_spill(float& slack)
+{
+	slack = slack * 2 > kCapSdMax ? 0.0f : slack * 2;
+}
+
+// With timing on: the device times between the context's recorded events
+// ev[first] .. ev[last] into st -- ev[0..1] partitioning, ev[1..2] k_agg,
+// ev[2..3] the finalize.  After the synchronisation that follows them.
+static int stage_times(syzsig_ctx* ctx, int first, int last, syzsig_batch_stats* st)
+{
+	double* const ms[3] = {&st->part_ms, &st->probe_ms, &st->decide_ms};
+	for (int i = first; ctx->timing && i < last; i++) {
+		float t = 0;
+		SYZ_HIP(hipEventElapsedTime(&t, ctx->ev[i], ctx->ev[i + 1]));
+		*ms[i] += t;
+	}
+	return SYZSIG_OK;
+}
+
 static int agg_capped(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t c1, const LevelMap& lm,
                       uint64_t run_recs, const AggGeom& g, const AggSrc* xp, syzsig_batch_stats* st, AggOut* out,
                       bool* done)
@@ -2342,17 +2337,11 @@ static int agg_capped(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint6
 	SYZ_HIP(hipMemcpyAsync(hcp, r.dc, P * 4, hipMemcpyDeviceToHost, s));
 	SYZ_HIP(hipMemcpyAsync(hov, r.ovf, 4, hipMemcpyDeviceToHost, s));
 	SYZ_HIP(hipStreamSynchronize(s));
-	if (ctx->timing) {
-		float t0 = 0, t1 = 0;
-		SYZ_HIP(hipEventElapsedTime(&t0, ctx->ev[0], ctx->ev[1]));
-		SYZ_HIP(hipEventElapsedTime(&t1, ctx->ev[1], ctx->ev[2]));
-		st->part_ms += t0;
-		st->probe_ms += t1;
-	}
+	SYZ_TRY(stage_times(ctx, 0, 2, st));
 	if (*hov) {
 		st->retries++;
 		if (!tight)
-			slack = slack * 2 > kCapSdMax ? 0.0f : slack * 2;
+			cap_slack_after_spill(slack);
 		return SYZSIG_OK;
 	}
 	uint64_t D = 0;
@@ -2483,13 +2472,7 @@ int agg_aggregate(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t 
 	SYZ_HIP(hipStreamSynchronize(s));
 	const std::vector<uint32_t> hc(hcp, hcp + P);
 	const std::vector<uint64_t> hb(hbp, hbp + P + 1);
-	if (ctx->timing) {
-		float t0 = 0, t1 = 0;
-		SYZ_HIP(hipEventElapsedTime(&t0, ctx->ev[0], ctx->ev[1]));
-		SYZ_HIP(hipEventElapsedTime(&t1, ctx->ev[1], ctx->ev[2]));
-		st->part_ms += t0;
-		st->probe_ms += t1;
-	}
+	SYZ_TRY(stage_times(ctx, 0, 2, st));
 	uint64_t D = 0, ovrec = 0;
 	std::vector<uint32_t> ovl;
 	for (uint32_t p = 0; p < P; p++) {
@@ -2617,6 +2600,24 @@ static int seed_pair_counter(syzsig_ctx* ctx, uint64_t npairs)
 	return SYZSIG_OK;
 }
 
+// What every finalize kernel takes: the run, the two tables, the outputs.
+static FinArgs fin_tables(syzsig_ctx* ctx, const syzsig_set* ms, const syzsig_set* nsp, const LevelMap& lm, uint64_t c0,
+                          const syzsig_batch* b, uint64_t* pairs)
+{
+	FinArgs fa{};
+	fa.lm = lm;
+	fa.c0 = c0;
+	fa.slots = ms->slots;
+	fa.bmask = ms->nbuckets - 1;
+	fa.ns_slots = nsp->slots;
+	fa.ns_bmask = nsp->nbuckets - 1;
+	fa.call_new = b->call_new;
+	fa.pairs = pairs;
+	fa.npairs = &ctx->d_cnt[kCntAux2];
+	fa.ctr = ctx->d_cnt;
+	return fa;
+}
+
 // The slice-exclusive finalize's arguments for a run of 2^pbits partitions and
 // at most n distinct elements (the deferred lists' capacity): both tables have
 // at least a bucket per partition.
@@ -2626,33 +2627,62 @@ static int fin_args(syzsig_ctx* ctx, const syzsig_set* ms, const syzsig_set* nsp
 	void *dd, *dn;
 	SYZ_TRY(ws_get(ctx, kWsFinDefer, n * 20 + 64, &dd));
 	SYZ_TRY(ws_get(ctx, kWsFinDeferNs, n * 8 + 64, &dn));
-	*fa = FinArgs{lm, c0, ms->slots, ms->nbuckets - 1, (63 - __builtin_clzll(ms->nbuckets)) - pbits, nsp->slots,
-	              nsp->nbuckets - 1, (63 - __builtin_clzll(nsp->nbuckets)) - pbits, b->call_new, pairs,
-	              &ctx->d_cnt[kCntAux2], ctx->d_cnt, (uint32_t*)dd, (uint4*)((char*)dd + ((n * 4 + 15) & ~15ull)),
-	              &ctx->d_cnt[kCntDefer], (uint64_t*)dn, &ctx->d_cnt[kCntDeferNs], ctx->agg_dbg};
+	*fa = fin_tables(ctx, ms, nsp, lm, c0, b, pairs);
+	fa->ms_shift = (63 - __builtin_clzll(ms->nbuckets)) - pbits;
+	fa->ns_shift = (63 - __builtin_clzll(nsp->nbuckets)) - pbits;
+	fa->def_e = (uint32_t*)dd;
+	fa->def_f = (uint4*)((char*)dd + ((n * 4 + 15) & ~15ull));
+	fa->def_cnt = &ctx->d_cnt[kCntDefer];
+	fa->def_ns = (uint64_t*)dn;
+	fa->def_ns_cnt = &ctx->d_cnt[kCntDeferNs];
+	fa->dbg = ctx->agg_dbg;
 	return SYZSIG_OK;
 }
 
 // The slice-exclusive finalize over the regions (all partitions), then the
-// deferred lists.  A one-sync run passes its void flag `spill`, the counter of
-// overflowed partitions and the gate past which nothing is committed.
+// deferred lists.
 // (The deferred lists in a launch of their own: taken by the finalize's last
 // block instead, they made the finalize 1.03 ms instead of 0.27 at C2.)
 static int fin_launch(syzsig_ctx* ctx, const FinArgs& fa, const uint32_t* dist_e, const uint4* dist_f,
-                      const uint32_t* cnt, uint32_t nregions, const uint32_t* spill = nullptr,
-                      unsigned long long* agg_ovf = nullptr, uint32_t gate = 0)
+                      const uint32_t* cnt, uint32_t nregions)
 {
 	const hipStream_t s = ctx->stream;
-	k_agg_finalize_x<2><<<nregions, kFxThreads, 0, s>>>(
-	    dist_e, dist_f, cnt, nregions, fa.lm, fa.c0, fa.slots, fa.bmask, fa.ms_shift, fa.ns_slots, fa.ns_bmask,
-	    fa.ns_shift, fa.call_new, fa.pairs, fa.npairs, fa.ctr, fa.def_e, fa.def_f, fa.def_cnt, fa.def_ns, fa.def_ns_cnt,
-	    fa.dbg, spill, agg_ovf, gate);
+	k_agg_finalize_x<2><<<nregions, kFxThreads, 0, s>>>(dist_e, dist_f, cnt, nregions, fa);
 	SYZ_HIP(hipGetLastError());
-	k_fin_deferred<<<2 * kDeferBlocks, 256, 0, s>>>(fa.def_e, fa.def_f, fa.def_cnt, fa.lm, fa.c0, fa.slots, fa.bmask,
-	                                                fa.ns_slots, fa.ns_bmask, fa.call_new, fa.pairs, fa.npairs, fa.ctr,
-	                                                fa.def_ns, fa.def_ns_cnt);
+	k_fin_deferred<<<2 * kDeferBlocks, 256, 0, s>>>(fa);
 	SYZ_HIP(hipGetLastError());
 	return SYZSIG_OK;
+}
+
+// The atomic finalize over any regions and tables (newSignal exists: the
+// callers have distinct elements to commit).
+static int fin_launch_atomic(syzsig_ctx* ctx, const syzsig_set* ms, const syzsig_set* nsp, const LevelMap& lm,
+                             uint64_t c0, const syzsig_batch* b, uint64_t* pairs, const uint32_t* dist_e,
+                             const uint4* dist_f, const uint32_t* cnt, uint32_t nregions)
+{
+	k_agg_finalize<<<nregions, kFinThreads, 0, ctx->stream>>>(dist_e, dist_f, cnt, nregions,
+	                                                          fin_tables(ctx, ms, nsp, lm, c0, b, pairs));
+	SYZ_HIP(hipGetLastError());
+	return SYZSIG_OK;
+}
+
+// The bookkeeping of a committed run: newSignal is kept when something
+// changed (else a set made for the run is dropped again), the tables' lengths
+// take the inserts, the stats the run.
+static void commit_run(syzsig_set* ms, syzsig_set* nsp, FreshNs& fresh, uint64_t inserted, uint64_t changed,
+                       uint64_t ns_ins, syzsig_batch_stats* st)
+{
+	if (changed)
+		fresh.keep();
+	else if (fresh.drop())
+		nsp = nullptr;
+	ms->len += inserted;
+	if (nsp)
+		nsp->len += ns_ins;
+	st->inserted += inserted;
+	st->changed += changed;
+	st->candidates += changed;
+	st->runs++;
 }
 
 // One triage run with one host synchronisation at the end ("the
@@ -2723,8 +2753,10 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 	// more overflowed partitions than this and the split path commits nothing:
 	// the run is redone with partitions sized from what k_agg counted
 	const uint32_t gate = P / 8;
-	SYZ_TRY(fin_launch(ctx, fa, (const uint32_t*)r.de, (const uint4*)r.df, (const uint32_t*)r.dc, P, r.ovf,
-	                   &ctx->d_cnt[kCntAggOvf], gate));
+	fa.spill = r.ovf;
+	fa.ovf_gate = &ctx->d_cnt[kCntAggOvf];
+	fa.gate_max = gate;
+	SYZ_TRY(fin_launch(ctx, fa, (const uint32_t*)r.de, (const uint4*)r.df, (const uint32_t*)r.dc, P));
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[3], s));
 	uint32_t* hov = (uint32_t*)(ctx->h_pin + kPinCounts);
@@ -2735,22 +2767,14 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 		*hov = (uint32_t)ctx->h_cnt[kCntSpill];
 		st->records = ctx->h_cnt[kCntRecords];
 	}
-	if (ctx->timing) {
-		float t0 = 0, t1 = 0, t2 = 0;
-		SYZ_HIP(hipEventElapsedTime(&t0, ctx->ev[0], ctx->ev[1]));
-		SYZ_HIP(hipEventElapsedTime(&t1, ctx->ev[1], ctx->ev[2]));
-		SYZ_HIP(hipEventElapsedTime(&t2, ctx->ev[2], ctx->ev[3]));
-		st->part_ms += t0;
-		st->probe_ms += t1;
-		st->decide_ms += t2;
-	}
+	SYZ_TRY(stage_times(ctx, 0, 3, st));
 	if (*hov & 6) {  // an optimistic run's assumptions failed: nothing committed
 		*assumed_bad = true;
 		return SYZSIG_OK;
 	}
 	if (*hov) {  // a cell spilled: nothing committed, redo with counted cells
 		st->retries++;
-		ctx->cap_sd = ctx->cap_sd * 2 > kCapSdMax ? 0.0f : ctx->cap_sd * 2;
+		cap_slack_after_spill(ctx->cap_sd);
 		return SYZSIG_OK;
 	}
 	if (ctx->h_cnt[kCntOverflow])
@@ -2830,11 +2854,8 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 			}
 			*pairs_out = (uint64_t*)pr;
 			SYZ_TRY(seed_pair_counter(ctx, npairs));
-			k_agg_finalize<<<(uint32_t)rc.size(), kFinThreads, 0, s>>>(
-			    (const uint32_t*)de2, (const uint4*)df2, (const uint32_t*)dc2, (uint32_t)rc.size(), lm, c0, ms->slots,
-			    ms->nbuckets - 1, nsp->slots, nsp->nbuckets - 1, b->call_new, (uint64_t*)pr, &ctx->d_cnt[kCntAux2],
-			    ctx->d_cnt);
-			SYZ_HIP(hipGetLastError());
+			SYZ_TRY(fin_launch_atomic(ctx, ms, nsp, lm, c0, b, (uint64_t*)pr, (const uint32_t*)de2, (const uint4*)df2,
+			                          (const uint32_t*)dc2, (uint32_t)rc.size()));
 			SYZ_TRY(counters_fetch(ctx));  // (synchronizes: rc is consumed)
 			if (ctx->h_cnt[kCntOverflow])
 				return fail(SYZSIG_EIO, "triage: table overflow after reserve (internal error; one-sync run, HBM partitions)");
@@ -2845,21 +2866,11 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 		}
 		st->overflow_parts += novf;
 	}
-	if (changed)
-		fresh.keep();
-	else if (fresh.drop())
-		nsp = nullptr;
-	ms->len += inserted;
-	if (nsp)
-		nsp->len += ns_ins;
-	inserted += inserted_done;
+	commit_run(ms, nsp, fresh, inserted, changed, ns_ins, st);
+	st->inserted += inserted_done;
 	st->distinct += D;
 	st->parts = P;
 	st->survivors += D;
-	st->inserted += inserted;
-	st->changed += changed;
-	st->candidates += changed;
-	st->runs++;
 	ctx->agg_distinct_ratio = run_recs ? (double)D / (double)run_recs : 0;
 	*npairs_io = npairs;
 	*done = true;
@@ -2876,7 +2887,7 @@ static int agg_triage_one_sync(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns,
 {
 	*done = false;
 	if (ctx->cap_sd <= 0 || ctx->agg_counted_once ||
-	    (ctx->agg_dbg & (SYZSIG_DEBUG_EXACT_CELLS | SYZSIG_DEBUG_CAP_SPILL | kDebugAtomicFinalize)))
+	    (ctx->agg_dbg & (SYZSIG_DEBUG_EXACT_CELLS | SYZSIG_DEBUG_CAP_SPILL)))
 		return SYZSIG_OK;
 	bool bad = false, regeom = false;
 	uint64_t retries0 = st->retries;
@@ -2927,41 +2938,22 @@ int agg_triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const syzsi
 		SYZ_HIP(hipEventRecord(ctx->ev[2], s));
 	// the slice-exclusive finalize when every region is a partition and both
 	// tables have at least one bucket per partition; else the atomic one
-	const bool fx = D && nsp && a.nregions == a.parts && ms->nbuckets >= a.parts && nsp->nbuckets >= a.parts &&
-	                !(ctx->agg_dbg & kDebugAtomicFinalize);
+	const bool fx = D && a.nregions == a.parts && ms->nbuckets >= a.parts && nsp->nbuckets >= a.parts;
 	if (fx) {
 		FinArgs fa;
 		SYZ_TRY(fin_args(ctx, ms, nsp, 31 - __builtin_clz(a.parts), lm, c0, b, (uint64_t*)pr, D, &fa));
 		SYZ_TRY(fin_launch(ctx, fa, a.dist_e, a.dist_f, a.cnt, a.nregions));
 	} else if (D) {
-		k_agg_finalize<<<a.nregions, kFinThreads, 0, s>>>(
-		    a.dist_e, a.dist_f, a.cnt, a.nregions, lm, c0, ms->slots,
-		    ms->nbuckets - 1, nsp ? nsp->slots : nullptr, nsp ? nsp->nbuckets - 1 : 0, b->call_new, (uint64_t*)pr,
-		    &ctx->d_cnt[kCntAux2], ctx->d_cnt);
+		SYZ_TRY(fin_launch_atomic(ctx, ms, nsp, lm, c0, b, (uint64_t*)pr, a.dist_e, a.dist_f, a.cnt, a.nregions));
 	}
-	SYZ_HIP(hipGetLastError());
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[3], s));
 	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->timing) {
-		float t = 0;
-		SYZ_HIP(hipEventElapsedTime(&t, ctx->ev[2], ctx->ev[3]));
-		st->decide_ms += t;
-	}
+	SYZ_TRY(stage_times(ctx, 2, 3, st));
 	if (ctx->h_cnt[kCntOverflow])
 		return fail(SYZSIG_EIO, "triage: table overflow after reserve (internal error; planned run)");
-	if (ctx->h_cnt[kCntChanged])
-		fresh.keep();
-	else if (fresh.drop())
-		nsp = nullptr;
-	ms->len += ctx->h_cnt[kCntInserted];
-	st->inserted += ctx->h_cnt[kCntInserted];
-	st->changed += ctx->h_cnt[kCntChanged];
-	st->candidates += ctx->h_cnt[kCntChanged];
-	if (nsp)
-		nsp->len += ctx->h_cnt[kCntAux];
+	commit_run(ms, nsp, fresh, ctx->h_cnt[kCntInserted], ctx->h_cnt[kCntChanged], ctx->h_cnt[kCntAux], st);
 	*npairs_io = ctx->h_cnt[kCntAux2];
-	st->runs++;
 	return SYZSIG_OK;
 }
 
@@ -3037,21 +3029,13 @@ int pairs_from_bits(syzsig_ctx* ctx, const syzsig_batch* b, const uint32_t* bits
 // (SURVEY.md 8(e) "local filter").
 constexpr uint32_t kMaxShardsAgg = 64;
 
+// the levels of an element's whole staircase (stair_walk without a cut), as a mask
 __device__ __forceinline__ uint32_t stair_levels(uint4 f4, uint32_t nlev)
 {
-	const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
-	uint32_t m = 0, mk = kAggNone;
-#pragma unroll
-	for (int l = 3; l >= 0; l--)
-		if (l < (int)nlev && f[l] < mk) {
-			mk = f[l];
-			m |= 1u << l;
-		}
+	uint32_t m = 0;
+	stair_walk(f4, (int)nlev - 1, [](int) { return false; }, [&](int l, uint32_t) { m |= 1u << l; });
 	return m;
 }
-
-
-
 
 // ---- the stream-ordered step's source side (syzsig_step_send_dev / _back_dev)
 // Staircase records into fixed buckets: owner g's at send[g * (cap + 1) + 1 ...],

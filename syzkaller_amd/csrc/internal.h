@@ -191,9 +191,6 @@ constexpr uint32_t kDebugResultPreserving =
     SYZSIG_DEBUG_RECS_GATE | SYZSIG_DEBUG_EDGE_MARKALL | SYZSIG_DEBUG_EDGE_PASSES | SYZSIG_DEBUG_AGG_IDX64;
 // ... and those a product build accepts: the above plus fault injection
 constexpr uint32_t kDebugAccepted = kDebugResultPreserving | SYZSIG_DEBUG_POLL_FAIL;
-// experiment builds only (outside kDebugAccepted): a planned triage run always,
-// finalized by the atomic kernel (no one-sync run, no slice-exclusive finalize)
-constexpr uint32_t kDebugAtomicFinalize = 16u;
 
 // capped cells of the aggregation path (agg.hip): default slack, in standard deviations
 constexpr float kCapSdDefault = 6.0f;

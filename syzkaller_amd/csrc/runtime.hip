@@ -143,7 +143,6 @@ int syzsig_ctx_create(int device, syzsig_ctx** out)
 		c->agg_dbg = (uint32_t)atoi(v);
 #ifndef SYZ_EXPERIMENTS
 		// a stray variable selects the accepted debug paths and nothing else
-		// (kDebugAtomicFinalize: experiment builds only)
 		c->agg_dbg &= syz::kDebugAccepted;
 #endif
 	}

@@ -13,7 +13,7 @@ Restated from csrc/agg.hip (the line each comes from):
   kAggSlots, kAggBW, kAggBuckets, kAggLimit   :61-67
   AggGeom.part / rec / resid                  :89, :94, :95
   agg_home_bucket                             :101-104
-  agg_group_size                              :2212-2218
+  agg_group_size                              :2188-2194
   cell_plan's capacity                        :994-995 (float arithmetic)
 and csrc/internal.h:198 kCapSdDefault, the slack a context starts with and
 syzsig_ctx_set_agg resets to (runtime.hip:218)."""
@@ -117,3 +117,45 @@ def fits_capped(counts, sd=CAP_SD):
     capped-cell run then is not redone with counted cells."""
     counts = np.asarray(counts)
     return bool((counts <= cell_capacity(counts.sum(axis=1), counts.shape[1], sd)[:, None]).all())
+
+
+# ---- the finalize's per-element decision, exhaustively (test_finalize_staircase_every_order)
+STAIR_ORDERS = 64   # ordered non-empty selections of the levels 0..3: 4 + 12 + 24 + 24
+STAIR_M0 = (None, 0, 1, 2, 3)   # M0[e]: absent, or a prio
+
+
+def staircase_cases():
+    """One element per (order of first appearance of its levels, M0 state):
+    64 x 5 = 320 elements.  Returns (elems, orders, batch, m0): elems[o * 5 + m]
+    has order orders[o] (a tuple of prios) and M0 state STAIR_M0[m]; batch =
+    (sigs, call_start, call_len, call_prio) of 17 calls in serial order --
+    call 4 * pos + prio holds the elements whose pos-th first appearance is at
+    prio, and call 16 (prio 0) repeats every element, a later dominated record
+    for each; m0 = (elems, prios) of maxSignal, sorted by element.
+
+    h = fmix32(e) is chosen so that the elements spread over 8 partitions (top
+    3 bits) and crowd a few home buckets of each table's slice: 4 per bucket of
+    a 2048-bucket table, 16 per bucket of a 512-bucket one (2 slots each), so
+    probe sequences leave the home bucket and inserts of one bucket race."""
+    from itertools import permutations
+
+    orders = [p for k in range(1, 5) for p in permutations(range(4), k)]
+    i = np.arange(len(orders) * len(STAIR_M0), dtype=np.uint64)
+    elems = fmix32_inv_np((((i % 8) << 29) | ((i // 8) << 19)).astype(np.uint32))
+    calls = [[] for _ in range(16)]
+    m0e, m0p = [], []
+    for o, order in enumerate(orders):
+        for m, prio0 in enumerate(STAIR_M0):
+            e = elems[o * len(STAIR_M0) + m]
+            for pos, prio in enumerate(order):
+                calls[4 * pos + prio].append(e)
+            if prio0 is not None:
+                m0e.append(e)
+                m0p.append(prio0)
+    calls = [np.array(c, np.uint32) for c in calls] + [elems.copy()]
+    hcnt = np.array([c.size for c in calls], np.uint32)
+    hcs = (np.cumsum(hcnt, dtype=np.uint64) - hcnt).astype(np.uint64)
+    hprio = np.array([c % 4 for c in range(16)] + [0], np.uint8)
+    m0e, m0p = np.array(m0e, np.uint32), np.array(m0p, np.int8)
+    k = np.argsort(m0e)
+    return elems, orders, (np.concatenate(calls), hcs, hcnt, hprio), (m0e[k], m0p[k])

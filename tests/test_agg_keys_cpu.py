@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests import agg_keys as AK
+from tests.table_keys import fmix32_np
 from tests.test_table_keys_cpu import _fmix32_int
 
 
@@ -109,3 +110,35 @@ def test_cell_capacity_and_fits_capped():
     assert AK.fits_capped(ok)
     ok[0, 3] = 129
     assert not AK.fits_capped(ok)
+
+
+def test_staircase_cases_cover_every_order_and_m0_state():
+    elems, orders, (hs, hcs, hcnt, hprio), (m0e, m0p) = AK.staircase_cases()
+    assert len(orders) == AK.STAIR_ORDERS == 64 and len(set(orders)) == 64
+    assert all(1 <= len(o) <= 4 and len(set(o)) == len(o) and set(o) <= {0, 1, 2, 3} for o in orders)
+    assert elems.size == 320 and np.unique(elems).size == 320
+    # every element's calls, read back from the batch: its order, then the dominated repeat
+    assert hcnt.size == 17 and hprio.tolist() == [0, 1, 2, 3] * 4 + [0] and int(hcnt.sum()) == hs.size == 1300
+    seen = {int(e): [] for e in elems}
+    for c in range(17):
+        rec = hs[int(hcs[c]):int(hcs[c]) + int(hcnt[c])]
+        assert np.unique(rec).size == rec.size
+        for e in rec:
+            seen[int(e)].append(int(hprio[c]))
+    m0 = dict(zip(m0e.tolist(), m0p.tolist()))
+    got = {(tuple(seen[int(e)][:-1]), m0.get(int(e))) for e in elems}
+    assert all(seen[int(e)][-1] == 0 for e in elems)
+    assert got == {(o, m) for o in orders for m in AK.STAIR_M0} and len(got) == 320
+    assert m0e.size == 256 and (np.diff(m0e.astype(np.int64)) > 0).all()
+    # 8 partitions of 40; 4 elements per home bucket of a 2048-bucket table
+    p, _ = AK.elem_home(elems, 3)
+    assert np.bincount(p, minlength=8).tolist() == [40] * 8
+    hb = np.bincount((fmix32_np(elems) >> np.uint32(21)).astype(np.int64))
+    assert set(hb[hb > 0].tolist()) == {4}
+    assert AK.fits_capped(AK.cell_counts(hs, hcs, hcnt, 3, 1))
+    # table sizes (table.hip buckets_for: the power of two >= n + 1, from 2): the
+    # planned run reserves for the 320 distinct elements and stays under 2048
+    # buckets; the one-sync run reserves for the 1300 records and reaches them
+    buckets_for = lambda n: max(2, 1 << int(n).bit_length())  # noqa: E731
+    assert buckets_for(256) == 512 and 256 + 320 <= 0.75 * 2 * 512 and buckets_for(320) == 512
+    assert buckets_for(256 + 1300) == 2048 and buckets_for(1300) == 2048

@@ -197,6 +197,51 @@ def test_triage_finalize_deferred_path(gpu, case):
         assert st["parts"] >= 8 and st["overflow_parts"] == 0, st
 
 
+@pytest.mark.parametrize("variant", ["slices", "deferred", "atomic"])
+def test_finalize_staircase_every_order(gpu, variant):
+    """The finalize's per-element decision on every case it has: 64 orders of
+    first appearance of the levels 0..3 x 5 states of M0[e] (absent, prio
+    0..3), one element each, every element with a later dominated record
+    (tests/agg_keys.py staircase_cases), through each of the three finalize
+    codes of csrc/agg.hip.  The stats do not say which kernel ran; the path
+    follows from the code (with per-record bits wanted, triage_batch_impl takes
+    the planned path: agg_triage_run):
+      slices    8 partitions: the one-sync run reserves both tables for the
+                run's 1300 records (2048 buckets each, >= 8), so
+                agg_triage_fused commits through fin_launch: k_agg_finalize_x.
+                (Were a cell to spill, the planned redo meets the same tables
+                and takes fin_launch too; no cell does, asserted.)
+      deferred  the same under SYZSIG_DEBUG_FIN_DEFER: a walk ends at its home
+                bucket, which 4 elements share and 2 fit, so at least half the
+                elements and half the newSignal merges go to k_fin_deferred.
+      atomic    2048 partitions and counted cells (SYZSIG_DEBUG_EXACT_CELLS:
+                agg_triage_one_sync returns at once -- its reservation for 1300
+                records would grow both tables to 2048 buckets, and the run
+                would take the slices).  agg_triage_run then reserves for the
+                320 distinct elements: maxSignal stays at the 512 buckets its
+                256 entries were given, newSignal is made with 512, both
+                < 2048 partitions: fin_launch_atomic, k_agg_finalize, with 16
+                elements racing for each home bucket.
+    (The table sizes are restated in test_agg_keys_cpu.py.)"""
+    from syzkaller_amd._lib import SYZSIG_DEBUG_EXACT_CELLS, SYZSIG_DEBUG_FIN_DEFER
+    from tests import agg_keys as AK
+
+    elems, orders, hb, m0 = AK.staircase_cases()
+    parts, dbg = {"slices": (8, 0), "deferred": (8, SYZSIG_DEBUG_FIN_DEFER),
+                  "atomic": (2048, SYZSIG_DEBUG_EXACT_CELLS)}[variant]
+    if parts == 8:
+        assert AK.fits_capped(AK.cell_counts(hb[0], hb[1], hb[2], 3, 1))
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(gpu.dev)  # noqa: E731
+    db = (t(hb[0], np.int32), t(hb[1], np.int64), t(hb[2], np.int32), t(hb[3], np.uint8))
+    gpu.eng.set_debug(dbg)
+    try:
+        st = compare(gpu, m0, hb, db, agg=2, parts=parts)
+    finally:
+        gpu.eng.set_debug(0)
+    assert st["parts"] == parts and st["distinct"] == elems.size and st["runs"] == 1, st
+    assert st["overflow_parts"] == 0 and st["retries"] == 0, st
+
+
 @pytest.mark.parametrize("mode", ["capped", "capped_split", "counted", "spill", "idx64", "counted_idx64", "edge_passes",
                                   "hot"])
 def test_triage_cell_layouts(gpu, mode):
