@@ -54,9 +54,9 @@
 //       so nothing is ever retried.
 //   k_pairs_mark (optional) per-record new bits from the pairs.
 #include <algorithm>
-#include <utility>
 #include <vector>
 
+#include "decide.h"
 #include "internal.h"
 
 namespace syz {
@@ -69,12 +69,10 @@ constexpr uint32_t kAggBuckets = kAggSlots / kAggBW;
 constexpr uint32_t kAggNoSlot = 0xFFFFFFFFu;
 static_assert(kAggRegion == kAggSlots, "distinct-list region per partition (internal.h)");
 constexpr uint32_t kAggLimit = kAggSlots * 4 / 5;  // distinct elements before a partition overflows
-static_assert(kAggLimit == kAggLimitRecs, "internal.h mirror");
 constexpr double kAggTargetLoad = 0.4;             // partitions are sized for this LDS load
 constexpr double kAggTargetLoadEntry = 0.6;        // ... and for Minimize
 constexpr uint64_t kMinItems = 2048;               // Minimize: at least this many partitioning work items
 constexpr uint32_t kAggEmpty = 0xFFFFFFFFu;        // empty key (LDS keys are residuals < 2^29)
-constexpr uint32_t kAggNone = 0xFFFFFFFFu;         // no record at this level
 constexpr uint32_t kAggOverflow = 0xFFFFFFFFu;     // partition count marker
 constexpr uint32_t kAggMinBits = 3, kAggMaxBits = 11;
 constexpr uint32_t kAggMaxParts = 1u << kAggMaxBits;
@@ -1198,7 +1196,7 @@ __device__ __forceinline__ bool agg_partition(AggLds& L, uint32_t p, const AggCe
 	for (uint32_t i = threadIdx.x; i < kAggSlots; i += blockDim.x) {
 		if (i < kAggSlots)
 			reinterpret_cast<uint32_t*>(kb)[i] = kAggEmpty;
-		fl[0][i] = fl[1][i] = fl[2][i] = fl[3][i] = kAggNone;
+		fl[0][i] = fl[1][i] = fl[2][i] = fl[3][i] = kNoFirst;
 	}
 	if (threadIdx.x == 0) {
 		L.s_n = 0;
@@ -1536,14 +1534,14 @@ __global__ __launch_bounds__(256) void k_agg_global_compact(const uint32_t* __re
 		const uint64_t i = i0 + threadIdx.x;
 		bool occ = false;
 		uint32_t h = kAggEmpty;
-		uint4 f = make_uint4(kAggNone, kAggNone, kAggNone, kAggNone);
+		uint4 f = make_uint4(kNoFirst, kNoFirst, kNoFirst, kNoFirst);
 		if (i <= C) {
 			f = make_uint4(gfl[i], gfl[(C + 1) + i], gfl[2 * (C + 1) + i], gfl[3 * (C + 1) + i]);
 			if (i < C) {
 				h = gkeys[i];
 				occ = h != kAggEmpty;
 			} else {
-				occ = (f.x & f.y & f.z & f.w) != kAggNone;
+				occ = (f.x & f.y & f.z & f.w) != kNoFirst;
 			}
 		}
 		const uint64_t m = __ballot(occ);
@@ -1560,7 +1558,8 @@ __global__ __launch_bounds__(256) void k_agg_global_compact(const uint32_t* __re
 
 // ---------------------------------------------------------------- finalize
 // checkNewSignal's decision for one distinct element e with level firsts f4,
-// in pieces that the three finalize codes compose:
+// in pieces that the three finalize codes compose (fin_top, fin_raises and
+// stair_walk are in decide.h: the records path of recs.hip composes them too):
 //   fin_top      the top level present; M_final[e] can only become P = lm.val[top]
 //   (the slot)   e's maxSignal slot, found or inserted -- the one step that
 //                differs: global atomics (fin_commit_atomic, for k_agg_finalize
@@ -1595,67 +1594,6 @@ struct FinArgs {
 	const unsigned long long* ovf_gate;
 	uint32_t gate_max;
 };
-
-// What a finalize kernel counts, and its epilogue.
-struct FinCounts {
-	uint64_t inserted = 0, changed = 0, ns_ins = 0, ovf = 0;
-	// every thread of the block (kOvf = false: the kernel cannot overflow a table)
-	template <bool kOvf = true>
-	__device__ __forceinline__ void report(unsigned long long* ctr) const
-	{
-		block_count(&ctr[kCntInserted], inserted);
-		block_count(&ctr[kCntChanged], changed);
-		block_count(&ctr[kCntAux], ns_ins);
-		if (kOvf)
-			block_count(&ctr[kCntOverflow], ovf);
-	}
-};
-
-// the top level present among the run's lm.n, or -1 (none, or !valid)
-__device__ __forceinline__ int fin_top(uint4 f4, const LevelMap& lm, bool valid)
-{
-	const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
-	int top = -1;
-#pragma unroll
-	for (int l = 0; l < 4; l++)
-		if (valid && l < (int)lm.n && f[l] != kAggNone)
-			top = l;
-	return top;
-}
-
-// p0 = M0[e] from the word `old` of e's maxSignal slot (0: inserted or claimed
-// just now; an "absent" marker is not live).  True when P raises it, counted.
-__device__ __forceinline__ bool fin_raises(uint64_t old, int8_t P, FinCounts& n, int& p0)
-{
-	const bool present = slot_live(old);
-	p0 = present ? (int)slot_prio(old) : -1000;
-	if ((int)P <= p0)
-		return false;
-	n.inserted += !present;  // fresh, or an "absent" marker going live
-	n.changed++;
-	return true;
-}
-
-// The staircase of an element's level firsts: from level `top` down, the
-// first records of strictly rising level -- each earlier than every record of
-// a higher level -- as on(level, first).  cut(level) ends the walk there.
-template <typename Cut, typename On>
-__device__ __forceinline__ void stair_walk(uint4 f4, int top, Cut cut, On on)
-{
-	const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
-	uint32_t mk = kAggNone;
-#pragma unroll
-	for (int l = 3; l >= 0; l--) {
-		if (l > top || f[l] == kAggNone)
-			continue;
-		if (cut(l))
-			break;
-		if (f[l] < mk) {
-			mk = f[l];
-			on(l, f[l]);
-		}
-	}
-}
 
 // The staircase above M0[e] = p0 holds e's new records: their calls are
 // flagged and put(call << 32 | e) takes the pairs.
@@ -2297,15 +2235,26 @@ static int cap_scatter_agg(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, 
 // kCapSdMax), or a partition overflowed the LDS table (its HBM fallback reads
 // counted cells).
 constexpr float kCapSdMax = 24.0f;
-static void cap_slack_after_spill(float& slack)
+void cap_slack_after_spill(float& slack)
 {
 	slack = slack * 2 > kCapSdMax ? 0.0f : slack * 2;
+}
+
+// After novf of a run's P LDS partitions overflowed (D distinct elements
+// counted in the others): the distinct-ratio guess was low, and the next runs
+// are sized for at least what was seen -- an overflowed partition held more
+// than kAggLimit; when most overflowed, what they held is unknown, so for the
+// worst case, one distinct element per record.
+void distinct_ratio_after_overflow(syzsig_ctx* ctx, uint64_t P, uint64_t novf, uint64_t D, uint64_t recs)
+{
+	const double seen = novf * 2 >= P ? (double)recs : (double)D + 2.0 * (double)novf * kAggLimit;
+	ctx->agg_distinct_ratio = std::max(ctx->agg_distinct_ratio, seen / (double)std::max<uint64_t>(recs, 1));
 }
 
 // With timing on: the device times between the context's recorded events
 // ev[first] .. ev[last] into st -- ev[0..1] partitioning, ev[1..2] k_agg,
 // ev[2..3] the finalize.  After the synchronisation that follows them.
-static int stage_times(syzsig_ctx* ctx, int first, int last, syzsig_batch_stats* st)
+int stage_times(syzsig_ctx* ctx, int first, int last, syzsig_batch_stats* st)
 {
 	double* const ms[3] = {&st->part_ms, &st->probe_ms, &st->decide_ms};
 	for (int i = first; ctx->timing && i < last; i++) {
@@ -2570,26 +2519,6 @@ static int reserve_slices(syzsig_ctx* ctx, syzsig_set* s, const uint32_t* dist_e
 	return SYZSIG_OK;
 }
 
-// A newSignal set made for this run (newSignal.Merge allocates a nil receiver,
-// signal.go:121-125 -- but only when some DiffRaw is non-empty): dropped again,
-// *ns back to nil, on every return that does not keep() it.
-struct FreshNs {
-	syzsig_set** ns;
-	bool armed;
-	FreshNs(syzsig_set** p, bool fresh) : ns(p), armed(fresh) {}
-	FreshNs(const FreshNs&) = delete;
-	~FreshNs() { drop(); }
-	void keep() { armed = false; }
-	bool drop()  // true: the set was this run's and is gone
-	{
-		if (armed) {
-			syzsig_set_free(*ns);
-			*ns = nullptr;
-		}
-		return std::exchange(armed, false);
-	}
-};
-
 // Zero the counters, with the pair cursor (kCntAux2) at npairs: the finalize
 // kernels append the run's pairs after the batch's earlier ones.
 static int seed_pair_counter(syzsig_ctx* ctx, uint64_t npairs)
@@ -2664,25 +2593,6 @@ static int fin_launch_atomic(syzsig_ctx* ctx, const syzsig_set* ms, const syzsig
 	                                                          fin_tables(ctx, ms, nsp, lm, c0, b, pairs));
 	SYZ_HIP(hipGetLastError());
 	return SYZSIG_OK;
-}
-
-// The bookkeeping of a committed run: newSignal is kept when something
-// changed (else a set made for the run is dropped again), the tables' lengths
-// take the inserts, the stats the run.
-static void commit_run(syzsig_set* ms, syzsig_set* nsp, FreshNs& fresh, uint64_t inserted, uint64_t changed,
-                       uint64_t ns_ins, syzsig_batch_stats* st)
-{
-	if (changed)
-		fresh.keep();
-	else if (fresh.drop())
-		nsp = nullptr;
-	ms->len += inserted;
-	if (nsp)
-		nsp->len += ns_ins;
-	st->inserted += inserted;
-	st->changed += changed;
-	st->candidates += changed;
-	st->runs++;
 }
 
 // One triage run with one host synchronisation at the end ("the
@@ -2785,13 +2695,9 @@ static int agg_triage_fused(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, co
 	uint64_t npairs = ctx->h_cnt[kCntAux2];
 	const uint64_t novf = ctx->h_cnt[kCntAggOvf];
 	if (novf > gate) {
-		// too few partitions (the distinct-ratio guess was low): nothing was
-		// committed; the next attempt sizes them for at least what was seen
-		// (an overflowed partition held more than kAggLimit)
-		// (most partitions overflowed: what they held is unknown, so size for the
-		// worst case, one distinct element per record)
-		const double seen = novf * 2 >= P ? (double)run_recs : (double)D + 2.0 * (double)novf * kAggLimit;
-		ctx->agg_distinct_ratio = std::max(ctx->agg_distinct_ratio, seen / (double)std::max<uint64_t>(run_recs, 1));
+		// too few partitions: nothing was committed; the next attempt sizes them
+		// for at least what was seen
+		distinct_ratio_after_overflow(ctx, P, novf, D, run_recs);
 		st->retries++;
 		*regeom = true;
 		return SYZSIG_OK;
@@ -3028,14 +2934,6 @@ int pairs_from_bits(syzsig_ctx* ctx, const syzsig_batch* b, const uint32_t* bits
 // result, at <= 4 records per distinct element instead of every record
 // (SURVEY.md 8(e) "local filter").
 constexpr uint32_t kMaxShardsAgg = 64;
-
-// the levels of an element's whole staircase (stair_walk without a cut), as a mask
-__device__ __forceinline__ uint32_t stair_levels(uint4 f4, uint32_t nlev)
-{
-	uint32_t m = 0;
-	stair_walk(f4, (int)nlev - 1, [](int) { return false; }, [&](int l, uint32_t) { m |= 1u << l; });
-	return m;
-}
 
 // ---- the stream-ordered step's source side (syzsig_step_send_dev / _back_dev)
 // Staircase records into fixed buckets: owner g's at send[g * (cap + 1) + 1 ...],

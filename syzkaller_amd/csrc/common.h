@@ -48,6 +48,8 @@ SYZ_HD uint32_t slot_key(uint64_t s) { return (uint32_t)(s >> 32); }
 SYZ_HD bool slot_live(uint64_t s) { return (s & kStateHasPrio) != 0; }
 SYZ_HD int8_t slot_prio(uint64_t s) { return (int8_t)((uint8_t)s ^ 0x80u); }
 SYZ_HD uint32_t prio_biased(int8_t p) { return (uint8_t)p ^ 0x80u; }
+// an absent element's prio where prios are compared as int: below every int8 (Go's `!ok`, signal.go:93-95)
+constexpr int kPrioAbsent = -1000;
 
 // murmur3 fmix32: bucket index of an element inside one table.
 SYZ_HD uint32_t fmix32(uint32_t h)

@@ -33,7 +33,7 @@
 //                          corpusCover -- one launch, after every allocation
 //   ni_accept_sequential   the reference loop over the set ops on clones, for a
 //                          batch past 2^23 entries or a partition past
-//                          kRpGroupCap; swapped in only at the end
+//                          kRpCap; swapped in only at the end
 // Per-key merge (both paths): each touched key's rows laid consecutively in
 // arrival order (host), then
 //   k_ni_gather            keys elem << 32 | index-in-group, and per entry its
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kNiThreads) void k_ni_reduce(const uint64_t* __rest
 				tot += s_w[it][x];
 			}
 			if (head) {
-				int m = -1000;
+				int m = kPrioAbsent;
 				uint32_t row_next = 0;
 				for (uint64_t q = i; q < n && (uint32_t)(s[q] >> 32) == e; q++) {
 					const uint32_t idx = (uint32_t)s[q], row = q == i ? ent_row[gb + idx] : row_next;
@@ -290,7 +290,7 @@ struct NiAccept {
 // The reference loop itself (manager.go:976-998), one input after the other
 // over the set ops, on clones of corpusSignal and corpusCover: the exact path
 // for a batch past kNiMaxEntries or with an element partition past
-// kRpGroupCap.  Nothing the caller holds is touched; ni_commit swaps the
+// kRpCap.  Nothing the caller holds is touched; ni_commit swaps the
 // clones in.
 static int ni_accept_sequential(syzsig_ctx* ctx, const NiBatch& B, syzsig_set* corpus_signal, syzsig_set* corpus_cover,
                                 uint8_t* acc, NiAccept* A)
@@ -326,7 +326,7 @@ static int ni_accept_sequential(syzsig_ctx* ctx, const NiBatch& B, syzsig_set* c
 }
 
 // The batched acceptance: acc[i] for the non-PRESENT rows, the events left on
-// the device.  *spilled: a partition past kRpGroupCap (nothing usable).
+// the device.  *spilled: a partition past kRpCap (nothing usable).
 static int ni_accept_batched(syzsig_ctx* ctx, const NiBatch& B, const syzsig_set* cs, uint64_t nA, uint8_t* acc,
                              NiAccept* A, bool* spilled)
 {

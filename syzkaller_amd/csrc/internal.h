@@ -7,6 +7,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <utility>
 
 #include "../../include/syzsig.h"
 #include "common.h"
@@ -157,7 +158,8 @@ enum WsSlot : int {
 	kWsNiAccepted = 47,
 	// the sort-unique of cover.hip, of the comparison hints and of the triage items (comps.hip,
 	// items.hip: with kWsSuStage2)
-	// | rp_group, the LDS grouping for Poll (recs.hip)
+	// | rp_group, the LDS grouping for Poll (recs.hip): its one segment and its
+	// keys; the partition front end's cell counts and bases (rp_partition)
 	kWsSuMeta = 48,
 	kWsRpgSeg = 48,
 	kWsSuTab = 49,
@@ -174,10 +176,10 @@ enum WsSlot : int {
 	kWsNiItems = 54,
 	// the sharded step (agg.hip, recs.hip) and the LDS records path (recs.hip)
 	kWsStepPairs = 55,
-	kWsRpKeys = 56,
-	kWsRpCounts = 57,
-	kWsRpBase = 58,
-	kWsRpSeg = 59,
+	kWsRpKeys = 56,    // rp_run: the keys, the records' slots, the element arrays
+	kWsRpCounts = 57,  // rp_partition for rp_run: the cell counts / offsets ...
+	kWsRpBase = 58,    // ... the partition bases; behind them rp_run's per-partition sums
+	kWsRpSeg = 59,     // rp_triage_records: its one segment
 	kWsStepShards = 60,
 	kWsStepRecs = 61,
 	kWsStepFlags = 62,
@@ -237,6 +239,7 @@ struct syzsig_ctx {
 	syzsig_set* step_ms = nullptr;         // the owner's shard and newSignal until finish
 	syzsig_set* step_ns = nullptr;
 	uint64_t step_parts = 0;
+	bool step_own_exact = false;           // the owner step took the per-record path, which commits the lengths itself
 	uint64_t step_src_parts = 1;           // the source run's aggregation partitions
 	bool step_own_timed = false, step_src_timed = false, step_back_timed = false;
 	hipEvent_t ev_step[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -303,7 +306,6 @@ int level_map_from_levels(const int8_t* levels, uint32_t nlevels, LevelMap* lm);
 
 // aggregation path (agg.hip)
 constexpr uint32_t kAggRegion = 7424;  // distinct-list region per partition (= LDS slots of k_agg)
-constexpr uint32_t kAggLimitRecs = kAggRegion * 4 / 5;  // distinct elements an LDS partition holds (agg.hip kAggLimit)
 struct AggOut {
 	const uint32_t* dist_e;  // distinct elements; region r at [r * kAggRegion, + cnt[r])
 	const uint4* dist_f;     // their first serial per level (0xFFFFFFFF = none)
@@ -337,6 +339,12 @@ int agg_triage_optimistic(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, cons
                           syzsig_batch_stats* st, uint64_t** pairs, uint64_t* npairs, bool* done);
 int agg_mark_bits(syzsig_ctx* ctx, const syzsig_batch* b, uint64_t c0, uint64_t c1, const uint64_t* pairs,
                   uint64_t p0, uint64_t p1);
+// The run policy (agg.hip), for a batch's runs and the sharded step's source run:
+// after a capped cell spilled, more slack (0 = counted cells from now on); after
+// novf of P LDS partitions overflowed (D distinct in the others), a larger ratio.
+int stage_times(syzsig_ctx* ctx, int first, int last, syzsig_batch_stats* st);  // timing on: ev[first..last] into st
+void cap_slack_after_spill(float& slack);
+void distinct_ratio_after_overflow(syzsig_ctx* ctx, uint64_t P, uint64_t novf, uint64_t D, uint64_t recs);
 // records mode (triage.hip: the per-record path, and the entry; recs.hip: the LDS path)
 int triage_records_impl(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const uint64_t* recs, uint64_t nrec,
                         const int8_t* levels, uint32_t nlevels, uint8_t* new_flags, syzsig_batch_stats* st,
@@ -348,9 +356,9 @@ int rp_triage_records(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const ui
 // partitions of recs.hip, for Poll (poll.hip): on return (enqueued only)
 // keys[base[p] .. base[p + 1]) = h_residual << 32 | r of partition p's entries
 // (partition = the top pbits of fmix32(e)), base on device (P + 1 entries);
-// ctr zeroed, then ctr[kCntSpill] != 0 when a partition exceeds kRpGroupCap
+// ctr zeroed, then ctr[kCntSpill] != 0 when a partition exceeds kRpCap
 // entries (nothing after it is valid).
-constexpr uint32_t kRpGroupCap = 2048;
+constexpr uint32_t kRpCap = 2048;  // records of one partition in LDS (recs.hip: local positions < 2^13)
 int rp_group(syzsig_ctx* ctx, const uint64_t* x, uint64_t n, uint64_t** keys, uint32_t** base, uint32_t* pbits,
              unsigned long long* ctr);
 // Stable LSD radix sort of n (u32 key, u32 value) pairs, keys < 2^key_bits
@@ -370,6 +378,50 @@ int pairs_from_bits(syzsig_ctx* ctx, const syzsig_batch* b, const uint32_t* bits
 constexpr double kMaxLoad = 0.75;
 constexpr double kTargetLoad = 0.5;
 constexpr double kHardLoad = 0.9;  // a reservation for a worst case grows the table only past this
+// after a run's inserts: the table grown when it is past kMaxLoad
+inline int set_grow_if_loaded(syzsig_set* s)
+{
+	return (double)s->len > kMaxLoad * (double)s->nslots() ? set_rehash(s, buckets_for(s->len), false) : SYZSIG_OK;
+}
+
+// A newSignal set made for this run (newSignal.Merge allocates a nil receiver,
+// signal.go:121-125 -- but only when some DiffRaw is non-empty): dropped again,
+// *ns back to nil, on every return that does not keep() it.
+struct FreshNs {
+	syzsig_set** ns;
+	bool armed;
+	FreshNs(syzsig_set** p, bool fresh) : ns(p), armed(fresh) {}
+	FreshNs(const FreshNs&) = delete;
+	~FreshNs() { drop(); }
+	void keep() { armed = false; }
+	bool drop()  // true: the set was this run's and is gone
+	{
+		if (armed) {
+			syzsig_set_free(*ns);
+			*ns = nullptr;
+		}
+		return std::exchange(armed, false);
+	}
+};
+
+// The bookkeeping of a committed run: newSignal is kept when something
+// changed (else a set made for the run is dropped again), the tables' lengths
+// take the inserts, the stats the run.
+inline void commit_run(syzsig_set* ms, syzsig_set* nsp, FreshNs& fresh, uint64_t inserted, uint64_t changed,
+                       uint64_t ns_ins, syzsig_batch_stats* st)
+{
+	if (changed)
+		fresh.keep();
+	else if (fresh.drop())
+		nsp = nullptr;
+	ms->len += inserted;
+	if (nsp)
+		nsp->len += ns_ins;
+	st->inserted += inserted;
+	st->changed += changed;
+	st->candidates += changed;
+	st->runs++;
+}
 
 inline int grid_for(uint64_t n, int block, int max_blocks = 2048)
 {

@@ -235,7 +235,7 @@ struct PollFresh {
 
 // The reference loop itself (manager.go:1027-1052), one poll after the other
 // over the set ops: the exact path for a batch whose entries crowd one element
-// partition past kRpGroupCap (a hot element polled thousands of times).
+// partition past kRpCap (a hot element polled thousands of times).
 // All or nothing, like the batched path: the loop runs on clones of
 // maxSignal and of every fuzzer's newMaxSignal, and only a loop that ran to
 // the end swaps them in and hands out the replies; on any error the clones

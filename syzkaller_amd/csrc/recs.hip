@@ -21,19 +21,20 @@
 //                 voids the run (the gate) before anything is committed
 //   k_rp_scatter  key = h_residual << 39 | serial << 15 | level << 13 | local
 //                 position, and the record's buffer index beside it
+//   (rp_partition issues these five, for rp_run and for Poll's rp_group)
 //   k_rp_agg / k_rp_elems / k_rp_flags
 //                 per partition an LDS hash of its elements with their level
 //                 firsts; per element one shard probe and the merges; per
-//                 record its flag in closed form (no ordering: see k_rp_agg).
+//                 record its flag (the decision of decide.h; no ordering: see k_rp_agg).
 // No device-scope atomics per record (those run at ~20 G/s chip-wide).
 #include <algorithm>
 #include <vector>
 
+#include "decide.h"
 #include "internal.h"
 
 namespace syz {
 
-constexpr uint32_t kRpCap = 2048;       // records of one partition in LDS (local positions < 2^13)
 constexpr uint32_t kRpTarget = 1024;    // partitions are sized for this mean
 constexpr uint32_t kRpMinBits = 7;      // h residuals of <= 25 bits fit the key
 constexpr uint32_t kRpMaxBits = 13;     // <= 32 KB of LDS counters per tile
@@ -186,10 +187,29 @@ __global__ __launch_bounds__(1024) void k_rp_coloffs(uint32_t* cnt, uint32_t nti
 	}
 }
 
+// The scatter's key formats: the key of record x (hr = its h residual) that
+// lies in slot `slot` of the source and goes to position pos, `local` inside
+// its partition (< kRpCap: the gate holds).
+struct RpKeyRec {  // rp_run: what k_rp_agg and k_rp_flags read, and the record's slot beside it
+	uint32_t* idx;
+	__device__ uint64_t operator()(uint64_t x, uint32_t hr, uint64_t slot, uint32_t pos, uint32_t local) const
+	{
+		idx[pos] = (uint32_t)slot;
+		return ((uint64_t)hr << 39) | ((x & kSerialMask) << 15) | (((x >> 24) & 3) << 13) | (local & kRpPosMask);
+	}
+};
+struct RpKeyEntry {  // rp_group: h_residual << 32 | the entry's index (the low word of x)
+	__device__ uint64_t operator()(uint64_t x, uint32_t hr, uint64_t, uint32_t, uint32_t) const
+	{
+		return ((uint64_t)hr << 32) | (uint32_t)x;
+	}
+};
+
+template <typename Key>
 __global__ __launch_bounds__(kRpTileThreads) void k_rp_scatter(RpSrc s, uint32_t pbits,
                                                                const uint32_t* __restrict__ off,
                                                                const uint32_t* __restrict__ base, uint64_t* keys,
-                                                               uint32_t* idx, const unsigned long long* ctr)
+                                                               Key key, const unsigned long long* ctr)
 {
 	extern __shared__ uint32_t cur[];  // P cursors
 	if (rp_gated(ctr))
@@ -204,14 +224,12 @@ __global__ __launch_bounds__(kRpTileThreads) void k_rp_scatter(RpSrc s, uint32_t
 	rp_tile(s, blockIdx.x, g, j0, n);
 	const uint64_t slot0 = g * s.stride + s.hdr + j0;
 	const uint64_t* r = s.recs + slot0;
-	const uint32_t rmask = pbits >= 32 ? 0u : (uint32_t)((1ull << (32 - pbits)) - 1);
+	const uint32_t rmask = (uint32_t)((1ull << (32 - pbits)) - 1);
 	for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) {
 		const uint64_t x = r[k];
 		const uint32_t h = fmix32((uint32_t)(x >> 32)), p = h >> (32 - pbits);
 		const uint32_t pos = atomicAdd(&cur[p], 1u);
-		const uint64_t local = (pos - base[p]) & kRpPosMask;  // < kRpCap: the gate holds
-		keys[pos] = ((uint64_t)(h & rmask) << 39) | ((x & kSerialMask) << 15) | (((x >> 24) & 3) << 13) | local;
-		idx[pos] = (uint32_t)(slot0 + k);
+		keys[pos] = key(x, h & rmask, slot0 + k, pos, pos - base[p]);
 	}
 }
 
@@ -225,10 +243,11 @@ struct RpTables {
 //     prio(l) > M0[e]  and  first[l] == s  and  first[l'] > s for every l' > l
 // (m before serial s is the max of M0 and the prios of the serials before s,
 // and a serial is one call, so one level; duplicates of an element in one call
-// share (s, l) and are flagged together, as DiffRaw collapses them), and the
-// final prio is max(M0[e], the top level present).  So the owner side is the
-// K3 aggregation again, without its scatter pass (the records arrive grouped
-// by partition from k_rp_scatter), in three kernels:
+// share (s, l) and are flagged together, as DiffRaw collapses them) -- (s, l)
+// is on the staircase of the firsts, above M0[e] -- and the final prio is
+// max(M0[e], the top level present).  So the owner side is the K3 aggregation
+// again, without its scatter pass (the records arrive grouped by partition
+// from k_rp_scatter), with the finalize's decision (decide.h), in three kernels:
 //   k_rp_agg    one workgroup per partition: an LDS hash of its elements (the h
 //               residual) with the level firsts (ds_min), its distinct
 //               elements written out at the partition's own offset (no
@@ -238,14 +257,14 @@ struct RpTables {
 //               shard probe and merges are latency chains that a
 //               partition-resident workgroup could only overlap ~80 at a time):
 //               M0[e], the merges, M0 kept for the flags;
-//   k_rp_flags  one thread per record: the closed form above.
+//   k_rp_flags  one thread per record: the condition above (stair_has).
 constexpr uint32_t kRpEmpty = 0xFFFFFFFFu;
-constexpr int16_t kRpAbsent = -32768;  // elem_m0 of an element absent from the shard
+constexpr int16_t kRpAbsent = -32768;  // kPrioAbsent as RpElems::m0 stores it
 
 struct RpElems {
 	uint32_t* e;      // element
-	uint4* f;         // level firsts (kSerialMask + 1 = none)
-	int16_t* m0;      // M0[e] (kRpAbsent: absent)
+	uint4* f;         // level firsts (kNoFirst = none)
+	int16_t* m0;      // M0[e] (kRpAbsent: kPrioAbsent)
 	uint32_t* rec_el; // per partitioned record: its element's index
 	uint32_t* ecnt;   // per partition: elements
 };
@@ -270,7 +289,7 @@ __global__ __launch_bounds__(kRpThreads) void k_rp_agg(const uint64_t* __restric
 	const uint32_t b0 = base[p], n = base[p + 1] - b0;
 	for (uint32_t i = tid; i < kRpCap; i += kRpThreads) {
 		L.key[i] = kRpEmpty;
-		L.fl[0][i] = L.fl[1][i] = L.fl[2][i] = L.fl[3][i] = kSerialMask + 1;
+		L.fl[0][i] = L.fl[1][i] = L.fl[2][i] = L.fl[3][i] = kNoFirst;
 	}
 	__syncthreads();
 	uint32_t sl[kPer];
@@ -357,32 +376,30 @@ __global__ __launch_bounds__(kRpElemThreads) void k_rp_elems(const uint32_t* __r
 	if (rp_gated(ctr))
 		return;
 	const uint32_t p = blockIdx.x, b0 = base[p], ne = el.ecnt[p];
-	uint32_t inserted = 0, changed = 0, ns_ins = 0, ovf = 0;
+	FinCounts n;
 	for (uint32_t j = threadIdx.x; j < ne; j += kRpElemThreads) {
 		const uint32_t i = b0 + j, e = el.e[i];
 		const Bucket bm = load_bucket(tb.ms + (home_bucket(e, tb.ms_bmask) << kBucketShift));
 		const Bucket bn = load_bucket(tb.ns + (home_bucket(e, tb.ns_bmask) << kBucketShift));
-		const uint4 f4 = el.f[i];
-		const int top = f4.w <= kSerialMask ? 3 : f4.z <= kSerialMask ? 2 : f4.y <= kSerialMask ? 1 : 0;
-		uint64_t v = 0;
+		// (top >= 0: an element has a record, and a record of a level >= lm.n
+		// gated the whole run in k_rp_count)
+		const int8_t P = lm.val[fin_top(el.f[i], lm, true)];
+		uint64_t v = 0;  // stays 0 (not live) when e is not found
 		const int64_t at = tbl_lookup_from(tb.ms, tb.ms_bmask, e, v, bm);
-		const bool present = at >= 0 && slot_live(v);
-		const int m0 = present ? (int)slot_prio(v) : -1000;  // absent: below every prio (signal.go:93-95)
-		el.m0[i] = present ? (int16_t)m0 : kRpAbsent;
-		const int m = max(m0, (int)lm.val[top]);
-		if (m > m0) {  // maxSignal.Merge / newSignal.Merge of the element's final prio
-			changed++;
-			inserted += !present;
+		int m0;
+		const bool raised = fin_raises(v, P, n, m0);
+		el.m0[i] = m0 == kPrioAbsent ? kRpAbsent : (int16_t)m0;
+		if (raised) {  // maxSignal.Merge / newSignal.Merge of the element's final prio
 			if (at >= 0)
-				tb.ms[at] = make_slot(e, (int8_t)m);  // e's only writer this launch
+				tb.ms[at] = make_slot(e, P);  // e's only writer this launch
 			else
-				ovf += tbl_merge(tb.ms, tb.ms_bmask, e, (int8_t)m) < 0;
-			const int r = tbl_merge_from(tb.ns, tb.ns_bmask, e, (int8_t)m, bn);
-			ns_ins += r == 1;
-			ovf += r < 0;
+				n.ovf += tbl_merge(tb.ms, tb.ms_bmask, e, P) < 0;
+			const int r = tbl_merge_from(tb.ns, tb.ns_bmask, e, P, bn);
+			n.ns_ins += r == 1;
+			n.ovf += r < 0;
 		}
 	}
-	const uint32_t v[kRpNumCnt] = {inserted, changed, ns_ins, ovf, 0};
+	const uint64_t v[kRpNumCnt] = {n.inserted, n.changed, n.ns_ins, n.ovf, 0};
 	const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
 #pragma unroll
 	for (uint32_t k = 0; k < kRpNumCnt; k++) {
@@ -424,7 +441,7 @@ __global__ __launch_bounds__(1024) void k_rp_reduce(const uint32_t* __restrict__
 		ctr[kRpCntIdx[threadIdx.x]] += acc[threadIdx.x];
 }
 
-// one thread per partitioned record: the flag in closed form
+// one thread per partitioned record: on its element's staircase, above M0[e]
 __global__ __launch_bounds__(256) void k_rp_flags(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
                                                   const uint32_t* __restrict__ base, uint32_t P, LevelMap lm,
                                                   RpElems el, uint8_t* flags, const unsigned long long* ctr)
@@ -437,15 +454,9 @@ __global__ __launch_bounds__(256) void k_rp_flags(const uint64_t* __restrict__ k
 		const uint32_t k = el.rec_el[i];
 		const int16_t m0 = el.m0[k];
 		const uint32_t lv = (uint32_t)(x >> 13) & 3, ser = (uint32_t)(x >> 15) & kSerialMask;
-		if ((int)lm.val[lv] <= (m0 == kRpAbsent ? -1000 : (int)m0))
+		if ((int)lm.val[lv] <= (m0 == kRpAbsent ? kPrioAbsent : (int)m0))
 			continue;
-		const uint4 f4 = el.f[k];
-		const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
-		bool nw = f[lv] == ser;
-#pragma unroll
-		for (uint32_t l = 0; l < 4; l++)
-			nw = nw && !(l > lv && f[l] <= ser);
-		if (nw)
+		if (stair_has(el.f[k], lv, ser))
 			flags[idx[i]] = 1;
 	}
 }
@@ -516,32 +527,66 @@ static uint32_t rp_pbits(uint64_t bound)
 	return pb;
 }
 
-// One LDS-partitioned records run over src (at most `bound` records), gated
-// and counted through ctr (the caller zeroed it or k_step_heads did).  Enqueues
-// only; the caller reads ctr after its synchronisation.  The shard and
-// newSignal must have room for `bound` more elements.
-int rp_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set* nsp, const RpSrc& src0, uint64_t bound, const LevelMap& lm,
-           uint8_t* flags, unsigned long long* ctr, uint32_t* pbits_out)
+// slots per tile: about <= 1024 tiles, so the tile x partition count matrix stays small
+static uint64_t rp_tile_slots(uint64_t slots)
 {
-	RpSrc src = src0;
+	return std::max<uint64_t>(kRpTileMin, (slots / 1024 + 4095) & ~4095ull);
+}
+
+struct RpParts {  // what rp_partition leaves
+	uint32_t pbits, P;
+	uint32_t* base;   // device, P + 1 entries: partition p's keys at [base[p], base[p + 1])
+	uint32_t* extra;  // device: the caller's extra_per_part words per partition
+};
+
+// The partition front end: src's records (at most `bound` < 2^32, tiles of
+// rp_tile_slots < 2^31: the callers checked) counted per tile and partition,
+// the cells placed, and the records' keys, in format Key, scattered to `keys`
+// (room for `bound`).  Gated and counted through ctr, which the caller zeroed
+// on the stream; nlev: levels >= it gate the run.  Enqueues only.
+template <typename Key>
+static int rp_partition(syzsig_ctx* ctx, RpSrc src, uint64_t bound, uint32_t nlev, int ws_counts, int ws_base,
+                        uint32_t extra_per_part, uint64_t* keys, Key key, unsigned long long* ctr, RpParts* out)
+{
 	const uint64_t seg_slots = src.stride - src.hdr;
-	const uint64_t slots = seg_slots * src.nseg;
-	// about <= 1024 tiles: the tile x partition count matrix stays small
-	const uint64_t tile = std::max<uint64_t>(kRpTileMin, (slots / 1024 + 4095) & ~4095ull);
-	if (tile >= (1ull << 31) || bound >= (1ull << 32))
-		return fail(SYZSIG_ERANGE, "records: too many records for the LDS path");
+	const uint64_t tile = rp_tile_slots(seg_slots * src.nseg);
 	src.tile = (uint32_t)tile;
 	src.tiles_per_seg = (uint32_t)std::max<uint64_t>(1, (seg_slots + tile - 1) / tile);
 	const uint64_t ntiles = (uint64_t)src.tiles_per_seg * src.nseg;
 	const uint32_t pbits = rp_pbits(bound), P = 1u << pbits;
-	*pbits_out = pbits;
-	void *wk, *wc, *wb;
+	void *wc, *wb;
+	SYZ_TRY(ws_get(ctx, ws_counts, ntiles * P * 4 + 256, &wc));
+	SYZ_TRY(ws_get(ctx, ws_base, (uint64_t)(kRpGroups + 3 + extra_per_part) * P * 4 + 256, &wb));
+	uint32_t* cnt = (uint32_t*)wc;
+	uint32_t* tot = (uint32_t*)wb;
+	uint32_t* base = tot + P;       // P + 1 entries
+	uint32_t* gsum = base + P + 2;  // kRpGroups x P
+	const hipStream_t s = ctx->stream;
+	const uint32_t cg = (P + 63) / 64;
+	k_rp_count<<<(uint32_t)ntiles, kRpTileThreads, P * 4, s>>>(src, pbits, nlev, cnt, ctr);
+	k_rp_colsum<<<cg, 1024, 0, s>>>(cnt, (uint32_t)ntiles, P, gsum, tot, ctr);
+	k_rp_scan<<<1, 1024, 0, s>>>(tot, P, base, ctr, ctx->agg_dbg & SYZSIG_DEBUG_RECS_GATE);
+	k_rp_coloffs<<<cg, 1024, 0, s>>>(cnt, (uint32_t)ntiles, P, gsum, base, ctr);
+	k_rp_scatter<<<(uint32_t)ntiles, kRpTileThreads, P * 4, s>>>(src, pbits, cnt, base, keys, key, ctr);
+	SYZ_HIP(hipGetLastError());
+	*out = RpParts{pbits, P, base, gsum + (uint64_t)kRpGroups * P};
+	return SYZSIG_OK;
+}
+
+// One LDS-partitioned records run over src (at most `bound` records), gated
+// and counted through ctr (the caller zeroed it or k_step_heads did).  Enqueues
+// only; the caller reads ctr after its synchronisation.  The shard and
+// newSignal must have room for `bound` more elements.
+int rp_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set* nsp, const RpSrc& src, uint64_t bound, const LevelMap& lm,
+           uint8_t* flags, unsigned long long* ctr, uint32_t* pbits_out)
+{
+	if (rp_tile_slots((src.stride - src.hdr) * src.nseg) >= (1ull << 31) || bound >= (1ull << 32))
+		return fail(SYZSIG_ERANGE, "records: too many records for the LDS path");
+	void* wk;
 	// per bound record: key 8 + index 4 + its element's index 4 + (as elements)
 	// element 4 + firsts 16 + M0 2
 	const uint64_t nb = (bound + 3) & ~3ull;  // array strides: the firsts stay 16-B aligned
 	SYZ_TRY(ws_get(ctx, kWsRpKeys, nb * 38 + 1024, &wk));
-	SYZ_TRY(ws_get(ctx, kWsRpCounts, ntiles * P * 4 + 256, &wc));
-	SYZ_TRY(ws_get(ctx, kWsRpBase, (uint64_t)(kRpGroups + 3 + kRpNumCnt) * P * 4 + 256, &wb));
 	uint64_t* keys = (uint64_t*)wk;
 	uint4* ef = (uint4*)(keys + nb);
 	uint32_t* idx = (uint32_t*)(ef + nb);
@@ -550,55 +595,19 @@ int rp_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set* nsp, const RpSrc& src0, 
 	el.rec_el = idx + nb;
 	el.e = el.rec_el + nb;
 	el.m0 = (int16_t*)(el.e + nb);
-	uint32_t* cnt = (uint32_t*)wc;
-	uint32_t* tot = (uint32_t*)wb;
-	uint32_t* base = tot + P;               // P + 1 entries
-	uint32_t* gsum = base + P + 2;          // kRpGroups x P
-	uint32_t* sums = gsum + (uint64_t)kRpGroups * P;  // kRpNumCnt per partition
-	el.ecnt = sums + (uint64_t)kRpNumCnt * P;
+	RpParts pt;
+	SYZ_TRY(rp_partition(ctx, src, bound, lm.n, kWsRpCounts, kWsRpBase, kRpNumCnt + 1, keys, RpKeyRec{idx}, ctr, &pt));
+	*pbits_out = pt.pbits;
+	uint32_t* sums = pt.extra;  // kRpNumCnt per partition
+	el.ecnt = sums + (uint64_t)kRpNumCnt * pt.P;
 	const hipStream_t s = ctx->stream;
-	const uint32_t cg = (P + 63) / 64;
-	k_rp_count<<<(uint32_t)ntiles, kRpTileThreads, P * 4, s>>>(src, pbits, lm.n, cnt, ctr);
-	k_rp_colsum<<<cg, 1024, 0, s>>>(cnt, (uint32_t)ntiles, P, gsum, tot, ctr);
-	k_rp_scan<<<1, 1024, 0, s>>>(tot, P, base, ctr, ctx->agg_dbg & SYZSIG_DEBUG_RECS_GATE);
-	k_rp_coloffs<<<cg, 1024, 0, s>>>(cnt, (uint32_t)ntiles, P, gsum, base, ctr);
-	k_rp_scatter<<<(uint32_t)ntiles, kRpTileThreads, P * 4, s>>>(src, pbits, cnt, base, keys, idx, ctr);
 	const RpTables tb{ms->slots, ms->nbuckets - 1, nsp->slots, nsp->nbuckets - 1};
-	k_rp_agg<<<P, kRpThreads, 0, s>>>(keys, base, pbits, el, ctr);
-	k_rp_elems<<<P, kRpElemThreads, 0, s>>>(base, lm, tb, el, ctr, sums);
-	k_rp_reduce<<<1, 1024, 0, s>>>(sums, P, ctr);
-	k_rp_flags<<<grid_for(bound, 256, 8192), 256, 0, s>>>(keys, idx, base, P, lm, el, flags, ctr);
+	k_rp_agg<<<pt.P, kRpThreads, 0, s>>>(keys, pt.base, pt.pbits, el, ctr);
+	k_rp_elems<<<pt.P, kRpElemThreads, 0, s>>>(pt.base, lm, tb, el, ctr, sums);
+	k_rp_reduce<<<1, 1024, 0, s>>>(sums, pt.P, ctr);
+	k_rp_flags<<<grid_for(bound, 256, 8192), 256, 0, s>>>(keys, idx, pt.base, pt.P, lm, el, flags, ctr);
 	SYZ_HIP(hipGetLastError());
 	return SYZSIG_OK;
-}
-
-}  // namespace syz
-
-namespace syz {
-
-// Poll's grouping (rp_group): key = h_residual << 32 | the entry's index
-__global__ __launch_bounds__(kRpTileThreads) void k_rp_scatter_idx(RpSrc s, uint32_t pbits,
-                                                                   const uint32_t* __restrict__ off,
-                                                                   uint64_t* keys, const unsigned long long* ctr)
-{
-	extern __shared__ uint32_t cur[];  // P cursors
-	if (rp_gated(ctr))
-		return;
-	const uint32_t P = 1u << pbits;
-	const uint32_t* row = off + (uint64_t)blockIdx.x * P;
-	for (uint32_t p = threadIdx.x; p < P; p += blockDim.x)
-		cur[p] = row[p];
-	__syncthreads();
-	uint32_t g;
-	uint64_t j0, n;
-	rp_tile(s, blockIdx.x, g, j0, n);
-	const uint64_t* r = s.recs + g * s.stride + s.hdr + j0;
-	const uint32_t rmask = (uint32_t)((1ull << (32 - pbits)) - 1);
-	for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) {
-		const uint64_t x = r[k];
-		const uint32_t h = fmix32((uint32_t)(x >> 32)), p = h >> (32 - pbits);
-		keys[atomicAdd(&cur[p], 1u)] = ((uint64_t)(h & rmask) << 32) | (uint32_t)x;
-	}
 }
 
 __global__ void k_rp_one_seg(uint64_t* seg, uint64_t n, unsigned long long* ctr)
@@ -609,40 +618,22 @@ __global__ void k_rp_one_seg(uint64_t* seg, uint64_t n, unsigned long long* ctr)
 		seg[0] = n;
 }
 
-static_assert(kRpGroupCap == kRpCap, "internal.h mirror");
-
+// Poll's grouping: the entries as one segment, keys in RpKeyEntry's format
 int rp_group(syzsig_ctx* ctx, const uint64_t* x, uint64_t n, uint64_t** keys_out, uint32_t** base_out,
              uint32_t* pbits_out, unsigned long long* ctr)
 {
 	if (n >= (1ull << 32))
 		return fail(SYZSIG_ERANGE, "group: 2^32 entries or more");
-	void *wseg, *wk, *wc, *wb;
+	void *wseg, *wk;
 	SYZ_TRY(ws_get(ctx, kWsRpgSeg, 64, &wseg));
-	RpSrc src{x, n, 0, 1, (const uint64_t*)wseg, 0, 0};
-	const uint64_t tile = std::max<uint64_t>(kRpTileMin, (n / 1024 + 4095) & ~4095ull);
-	src.tile = (uint32_t)tile;
-	src.tiles_per_seg = (uint32_t)std::max<uint64_t>(1, (n + tile - 1) / tile);
-	const uint64_t ntiles = src.tiles_per_seg;
-	const uint32_t pbits = rp_pbits(n), P = 1u << pbits;
 	SYZ_TRY(ws_get(ctx, kWsRpgKeys, n * 8 + 64, &wk));
-	SYZ_TRY(ws_get(ctx, kWsRpgCounts, ntiles * P * 4 + 256, &wc));
-	SYZ_TRY(ws_get(ctx, kWsRpgBase, (uint64_t)(kRpGroups + 3) * P * 4 + 256, &wb));
-	uint32_t* cnt = (uint32_t*)wc;
-	uint32_t* tot = (uint32_t*)wb;
-	uint32_t* base = tot + P;       // P + 1 entries
-	uint32_t* gsum = base + P + 2;  // kRpGroups x P
-	const hipStream_t s = ctx->stream;
-	const uint32_t cg = (P + 63) / 64;
-	k_rp_one_seg<<<1, 64, 0, s>>>((uint64_t*)wseg, n, ctr);
-	k_rp_count<<<(uint32_t)ntiles, kRpTileThreads, P * 4, s>>>(src, pbits, 256, cnt, ctr);
-	k_rp_colsum<<<cg, 1024, 0, s>>>(cnt, (uint32_t)ntiles, P, gsum, tot, ctr);
-	k_rp_scan<<<1, 1024, 0, s>>>(tot, P, base, ctr, ctx->agg_dbg & SYZSIG_DEBUG_RECS_GATE);
-	k_rp_coloffs<<<cg, 1024, 0, s>>>(cnt, (uint32_t)ntiles, P, gsum, base, ctr);
-	k_rp_scatter_idx<<<(uint32_t)ntiles, kRpTileThreads, P * 4, s>>>(src, pbits, cnt, (uint64_t*)wk, ctr);
-	SYZ_HIP(hipGetLastError());
+	k_rp_one_seg<<<1, 64, 0, ctx->stream>>>((uint64_t*)wseg, n, ctr);
+	const RpSrc src{x, n, 0, 1, (const uint64_t*)wseg, 0, 0};
+	RpParts pt;
+	SYZ_TRY(rp_partition(ctx, src, n, 256, kWsRpgCounts, kWsRpgBase, 0, (uint64_t*)wk, RpKeyEntry{}, ctr, &pt));
 	*keys_out = (uint64_t*)wk;
-	*base_out = base;
-	*pbits_out = pbits;
+	*base_out = pt.base;
+	*pbits_out = pt.pbits;
 	return SYZSIG_OK;
 }
 
@@ -652,9 +643,9 @@ int rp_triage_records(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const ui
 	*done = false;
 	// room for every record's element changing, before anything is committed
 	SYZ_TRY(set_reserve(ms, nrec));
-	const bool fresh_ns = !*ns;
-	if (fresh_ns)
-		SYZ_TRY(syzsig_set_make(ctx, nrec, ns));  // newSignal.Merge allocates a nil receiver (signal.go:121-125)
+	FreshNs fresh(ns, !*ns);
+	if (fresh.armed)
+		SYZ_TRY(syzsig_set_make(ctx, nrec, ns));
 	syzsig_set* nsp = *ns;
 	SYZ_TRY(set_reserve_load(nsp, nrec, kHardLoad));
 	void* ws;
@@ -672,34 +663,15 @@ int rp_triage_records(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const ui
 	const uint64_t gate = ctx->h_cnt[kCntSpill];
 	if (gate & 4)
 		return fail(SYZSIG_EINVAL, "triage_records: a record's prio level is out of range");
-	if (gate) {  // a partition past the LDS capacity: nothing was committed
-		if (fresh_ns) {
-			syzsig_set_free(nsp);
-			*ns = nullptr;
-		}
+	if (gate)  // a partition past the LDS capacity: nothing was committed
 		return SYZSIG_OK;
-	}
 	if (ctx->h_cnt[kCntOverflow])
 		return fail(SYZSIG_EIO, "triage_records: table overflow after reserve (internal error)");
-	if (ctx->timing) {
-		float t = 0;
-		SYZ_HIP(hipEventElapsedTime(&t, ctx->ev[2], ctx->ev[3]));
-		st->decide_ms += t;
-	}
-	const uint64_t changed = ctx->h_cnt[kCntChanged];
-	ms->len += ctx->h_cnt[kCntInserted];
-	nsp->len += ctx->h_cnt[kCntAux];
-	if (fresh_ns && changed == 0) {
-		syzsig_set_free(nsp);
-		*ns = nullptr;
-	}
-	st->inserted += ctx->h_cnt[kCntInserted];
-	st->changed += changed;
-	st->candidates += changed;
+	SYZ_TRY(stage_times(ctx, 2, 3, st));
+	commit_run(ms, nsp, fresh, ctx->h_cnt[kCntInserted], ctx->h_cnt[kCntChanged], ctx->h_cnt[kCntAux], st);
 	st->distinct += ctx->h_cnt[kCntDistinct];
 	st->survivors += ctx->h_cnt[kCntDistinct];
 	st->parts = 1ull << pbits;
-	st->runs++;
 	*done = true;
 	return SYZSIG_OK;
 }
@@ -755,9 +727,11 @@ int syzsig_step_own_dev(syzsig_ctx* ctx, syzsig_set* shard, syzsig_set* new_sign
 			uint32_t pbits = 0;
 			SYZ_TRY(rp_run(ctx, shard, new_signal, src, bound, lm, d_flags, oc, &pbits));
 			ctx->step_parts = 1ull << pbits;
+			ctx->step_own_exact = false;
 		} else {
 			// the per-record path over this owner's records, compacted (host round trips)
 			ctx->step_parts = 0;
+			ctx->step_own_exact = true;
 			unsigned long long* hc = ctx->h_step + kStepOwn;
 			SYZ_HIP(hipMemcpyAsync(hc, oc, kNumCounters * 8, hipMemcpyDeviceToHost, s));
 			std::vector<uint64_t> cnt(nshards);
@@ -788,10 +762,9 @@ int syzsig_step_own_dev(syzsig_ctx* ctx, syzsig_set* shard, syzsig_set* new_sign
 					k_step_uncompact<<<grid_for(n, 256, 8192), 256, 0, s>>>((const uint8_t*)wf, slot, n, d_flags);
 					SYZ_HIP(hipGetLastError());
 				}
-				// the owner counters as the LDS path leaves them; the lengths are
-				// already committed by the per-record path
-				hc[kCntInserted] = 0;
-				hc[kCntAux] = 0;
+				// the owner counters as the LDS path leaves them (the lengths are
+				// already committed by the per-record path: step_own_exact)
+				hc[kCntInserted] = st.inserted;
 				hc[kCntChanged] = st.changed;
 				hc[kCntDistinct] = st.distinct;
 				hc[kCntRecords] = n;
@@ -828,16 +801,10 @@ int syzsig_step_finish(syzsig_ctx* ctx, syzsig_step_status* out)
 	// range or more records than assumed (4, k_cell_plan_fast) and LDS
 	// overflows send the source to its exact path, which validates and sizes
 	out->src_void = src[kCntSpill] & 2 ? 2 : src[kCntSpill] || src[kCntAggOvf] ? 1 : 0;
-	if (src[kCntSpill] & 1)  // a capped cell spilled: more slack for the next runs (as agg_capped does)
-		ctx->cap_sd = ctx->cap_sd * 2 > 24.0f ? 0.0f : ctx->cap_sd * 2;
-	if (!(src[kCntSpill] & 6) && src[kCntAggOvf] && src[kCntRecords]) {
-		// LDS partitions overflowed: the distinct-ratio guess was low; size the
-		// next runs for at least what was seen (as the one-sync triage run does)
-		const double P = (double)ctx->step_src_parts, novf = (double)src[kCntAggOvf];
-		const double seen = novf * 2 >= P ? (double)src[kCntRecords]
-		                                  : (double)src[kCntDistinct] + 2.0 * novf * kAggLimitRecs;
-		ctx->agg_distinct_ratio = std::max(ctx->agg_distinct_ratio, seen / (double)src[kCntRecords]);
-	}
+	if (src[kCntSpill] & 1)  // the source run's policy (agg.hip)
+		cap_slack_after_spill(ctx->cap_sd);
+	if (!(src[kCntSpill] & 6) && src[kCntAggOvf] && src[kCntRecords])
+		distinct_ratio_after_overflow(ctx, ctx->step_src_parts, src[kCntAggOvf], src[kCntDistinct], src[kCntRecords]);
 	out->global_void = bk[kCntError] != 0;
 	out->owners_void = out->global_void ? 0 : bk[kCntAux];
 	out->records = src[kCntRecords];
@@ -854,13 +821,15 @@ int syzsig_step_finish(syzsig_ctx* ctx, syzsig_step_status* out)
 			out->own_distinct = own[kCntDistinct];
 			out->inserted = own[kCntInserted];
 			out->changed = own[kCntChanged];
-			ctx->step_ms->len += own[kCntInserted];
-			ctx->step_ns->len += own[kCntAux];
+			if (!ctx->step_own_exact) {
+				ctx->step_ms->len += own[kCntInserted];
+				ctx->step_ns->len += own[kCntAux];
+			}
 			if (own[kCntOverflow])
 				rc = fail(SYZSIG_EIO, "step: table overflow after reserve (internal error)");
 		}
-		if ((double)ctx->step_ms->len > kMaxLoad * (double)ctx->step_ms->nslots() && rc == SYZSIG_OK)
-			rc = set_rehash(ctx->step_ms, buckets_for(ctx->step_ms->len), false);
+		if (rc == SYZSIG_OK)
+			rc = set_grow_if_loaded(ctx->step_ms);
 		ctx->step_ms->step_busy = ctx->step_ns->step_busy = false;
 		ctx->step_ms = ctx->step_ns = nullptr;
 		// the owner counters are consumed: a second finish must not commit them again

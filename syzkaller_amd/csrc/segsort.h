@@ -642,7 +642,7 @@ int su_sort_unique(syzsig_ctx* ctx, const SuSegs& S, const Pol& pol)
 
 // ---- sort-and-walk ----
 
-// One workgroup per element partition p (<= kRpGroupCap entries, keys
+// One workgroup per element partition p (<= kRpCap entries, keys
 // h_residual << 32 | entry index from rp_group).  The keys are sorted in LDS,
 // so each element's entries are one run in entry order -- arrival order of
 // their owners (polls, inputs), and inside an owner the Serial's order -- and
@@ -659,15 +659,15 @@ __device__ __forceinline__ void su_sort_walk(const uint64_t* __restrict__ keys, 
                                              uint64_t tbl_bmask, uint64_t* ev, uint64_t ev_cap,
                                              unsigned long long* nev, const unsigned long long* ctr, Event event)
 {
-	using Tile = SuWordsTile<1, kRpGroupCap>;
+	using Tile = SuWordsTile<1, kRpCap>;
 	__shared__ typename Tile::Lds t;
-	__shared__ uint64_t out[kRpGroupCap];
+	__shared__ uint64_t out[kRpCap];
 	__shared__ uint32_t s_n;
 	__shared__ unsigned long long s_base;
 	if (ctr[kCntSpill])
-		return;  // a partition past kRpGroupCap: the batch takes the sequential path
+		return;  // a partition past kRpCap: the batch takes the sequential path
 	const uint32_t p = blockIdx.x, tid = threadIdx.x, b0 = base[p], n = base[p + 1] - b0;
-	if (n == 0 || n > kRpGroupCap)
+	if (n == 0 || n > kRpCap)
 		return;
 	const uint64_t* k = t.k[0];
 	for (uint32_t i = tid; i < n; i += kSuThreads)
@@ -682,7 +682,7 @@ __device__ __forceinline__ void su_sort_walk(const uint64_t* __restrict__ keys, 
 			continue;  // not the head of e's run
 		const uint32_t e = fmix32_inv(hp | hr);
 		uint64_t v = 0;
-		int m = -1000;  // absent: below every prio (signal.go:79-81)
+		int m = kPrioAbsent;  // (signal.go:79-81)
 		if (tbl && tbl_lookup(tbl, tbl_bmask, e, v) >= 0 && slot_live(v))
 			m = slot_prio(v);
 		uint32_t owner_next = 0;

@@ -585,11 +585,7 @@ static int triage_run(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, Prep pre
 		if (ctx->timing)
 			SYZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
 		SYZ_TRY(counters_fetch(ctx));
-		if (ctx->timing) {
-			float ms = 0;
-			SYZ_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-			st->decide_ms += ms;
-		}
+		SYZ_TRY(stage_times(ctx, 2, 3, st));
 		if (ctx->h_cnt[kCntOverflow])
 			return fail(SYZSIG_EIO, "newSignal overflow (internal error)");
 		ms->len += ctx->h_cnt[kCntInserted];
@@ -679,8 +675,7 @@ int triage_batch_impl(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const sy
 	}
 	}
 finish:
-	if ((double)ms->len > kMaxLoad * (double)ms->nslots())
-		SYZ_TRY(set_rehash(ms, buckets_for(ms->len), false));
+	SYZ_TRY(set_grow_if_loaded(ms));
 	st->new_signal_len = syzsig_len(*ns);
 	st->new_pairs = npairs;
 	if (b->new_pairs && npairs && pairs != b->new_pairs) {
@@ -716,35 +711,29 @@ int triage_records_impl(syzsig_ctx* ctx, syzsig_set* ms, syzsig_set** ns, const 
 	if (nrec == 0)
 		return SYZSIG_OK;
 	SYZ_HIP(hipMemsetAsync(new_flags, 0, nrec, ctx->stream));
-	if (nrec >= (1ull << 20) && nrec < (1ull << 31) && ctx->part_mode != 0 && allow_lds) {
-		// partitioned by element through LDS (recs.hip); a partition past the LDS
-		// capacity (a hot element's records in a generic input) voids that run
-		// before anything is committed and the per-record path below runs instead
-		bool done = false;
+	// partitioned by element through LDS (recs.hip); a partition past the LDS
+	// capacity (a hot element's records in a generic input) voids that run
+	// before anything is committed and the per-record path runs instead
+	bool done = false;
+	if (nrec >= (1ull << 20) && nrec < (1ull << 31) && ctx->part_mode != 0 && allow_lds)
 		SYZ_TRY(rp_triage_records(ctx, ms, ns, recs, nrec, lm, new_flags, st, &done));
-		if (done) {
-			if ((double)ms->len > kMaxLoad * (double)ms->nslots())
-				SYZ_TRY(set_rehash(ms, buckets_for(ms->len), false));
-			st->new_signal_len = syzsig_len(*ns);
+	if (!done) {
+		SYZ_TRY(set_ensure_triage_state(ms));
+		const uint64_t nseg = (nrec + kSegRecs - 1) / kSegRecs;
+		void *cs, *cm, *cc;
+		SYZ_TRY(ws_get(ctx, kWsOp3, nrec * 4, &cs));
+		SYZ_TRY(ws_get(ctx, kWsCandMeta, nrec * 4, &cm));
+		SYZ_TRY(ws_get(ctx, kWsCandCount, nseg * 4, &cc));
+		auto prep = [&](RecsIn* in, int* grid, syzsig_batch_stats*) -> int {
+			in->recs = recs;
+			in->nrec = nrec;
+			in->new_flags = new_flags;
+			*grid = grid_for(nseg * 64, 256, 4096);
 			return SYZSIG_OK;
-		}
+		};
+		SYZ_TRY(triage_run<RecsIn>(ctx, ms, ns, prep, lm, (uint32_t*)cs, (uint32_t*)cm, (uint32_t*)cc, st));
 	}
-	SYZ_TRY(set_ensure_triage_state(ms));
-	const uint64_t nseg = (nrec + kSegRecs - 1) / kSegRecs;
-	void *cs, *cm, *cc;
-	SYZ_TRY(ws_get(ctx, kWsOp3, nrec * 4, &cs));
-	SYZ_TRY(ws_get(ctx, kWsCandMeta, nrec * 4, &cm));
-	SYZ_TRY(ws_get(ctx, kWsCandCount, nseg * 4, &cc));
-	auto prep = [&](RecsIn* in, int* grid, syzsig_batch_stats*) -> int {
-		in->recs = recs;
-		in->nrec = nrec;
-		in->new_flags = new_flags;
-		*grid = grid_for(nseg * 64, 256, 4096);
-		return SYZSIG_OK;
-	};
-	SYZ_TRY(triage_run<RecsIn>(ctx, ms, ns, prep, lm, (uint32_t*)cs, (uint32_t*)cm, (uint32_t*)cc, st));
-	if ((double)ms->len > kMaxLoad * (double)ms->nslots())
-		SYZ_TRY(set_rehash(ms, buckets_for(ms->len), false));
+	SYZ_TRY(set_grow_if_loaded(ms));
 	st->new_signal_len = syzsig_len(*ns);
 	return SYZSIG_OK;
 }

@@ -51,7 +51,7 @@ def test_poll_batch_vs_sequential_oracle(gpu, monkeypatch, seed, F, K, U, n, lim
 
 
 PBITS = 7  # csrc/recs.hip rp_pbits for a batch of at most 2^17 entries: partition = the top 7 bits of fmix32(e)
-GROUP_CAP = 2048  # csrc/internal.h kRpGroupCap
+GROUP_CAP = 2048  # csrc/internal.h kRpCap
 
 
 def _in_partition(rng, p, n):
@@ -64,7 +64,7 @@ def _in_partition(rng, p, n):
 def test_poll_batch_partition_sizes(gpu, case):
     """The LDS sort of k_poll_part_walk at its edges: partitions of exactly 1,
     2 and 3 entries (sorts of 1, 2 and 4 keys, the last one padded), and a
-    partition of exactly kRpGroupCap entries (the largest batched case: the
+    partition of exactly kRpCap entries (the largest batched case: the
     whole tile, no pad)."""
     from syzkaller_amd import signal as S
 
