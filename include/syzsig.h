@@ -535,6 +535,45 @@ int syzsig_corpus_add_inputs_dev(syzsig_ctx* ctx, const uint64_t* d_input_off, c
                                  uint64_t n_input, const int8_t* d_item_prio, uint64_t n_items,
                                  const uint8_t* d_item_keep, syzsig_set** corpus_signal, syzsig_set** max_signal);
 
+/* ---- syz-fuzzer/fuzzer.go:344-350: what the fuzzer does with the reply to its
+ * poll, over a batch of Serials ----
+ * Segment s is one Serial, d_elems / d_prios[seg_off[s] .. seg_off[s + 1]) (a
+ * range that is reversed or ends past n_entries is SYZSIG_EINVAL), in arrival
+ * order, with d_seg_kind[s]:
+ *  - SYZSIG_SEG_MAXSIGNAL: r.MaxSignal.  D = Deserialize(segment) (:344); if
+ *    D.Len() != 0, maxSignal.Merge(D) (addMaxSignal, :468-475);
+ *  - SYZSIG_SEG_INPUT: the Signal of one of r.NewInputs (at most 100 per poll,
+ *    syz-manager/manager.go:1053-1057).  D = Deserialize(segment)
+ *    (addInputFromAnotherFuzzer, :433-444); if !D.Empty(),
+ *    corpusSignal.Merge(D); maxSignal.Merge(D) (addInputToCorpus, :446-460).
+ * Deserialize (signal.go:58-71) assigns entry after entry, so D[e] is the prio
+ * of the LAST entry of e inside that segment, also when an earlier one is
+ * higher; prios are int8 and Merge keeps the maximum.  Max-merge commutes and
+ * is idempotent, so the batch is the sequential loop exactly, for the replies
+ * of any number of polls in one call.  A NULL *corpus_signal or *max_signal is
+ * nil and is allocated only if a non-empty segment reaches it (signal.go:
+ * 117-131): a batch of MAXSIGNAL segments leaves a nil corpusSignal nil.
+ * All or nothing: the segments are checked first, and room is reserved in both
+ * tables before the launches that commit; an error before them leaves both
+ * sets' contents (and NULL sets NULL) as they were.  The two sets must be
+ * distinct (SYZSIG_EINVAL); a kind above SYZSIG_SEG_INPUT is SYZSIG_EINVAL, a
+ * segment of 2^31 or more entries or 2^32 or more segments SYZSIG_ERANGE.
+ * SYZSIG_POLLRES_TILE: a segment of at most this many entries is resolved by
+ * one workgroup in LDS; a longer one (a Connect reply's MaxSignal) through a
+ * scratch table in the context's workspace. */
+#define SYZSIG_SEG_MAXSIGNAL 0u
+#define SYZSIG_SEG_INPUT 1u
+#define SYZSIG_POLLRES_TILE 4096
+int syzsig_fuzzer_poll_res_dev(syzsig_ctx* ctx, const uint64_t* d_seg_off, const uint8_t* d_seg_kind, uint64_t nseg,
+                               const uint32_t* d_elems, const int8_t* d_prios, uint64_t n_entries,
+                               syzsig_set** corpus_signal, syzsig_set** max_signal);
+/* Which paths the context's last syzsig_fuzzer_poll_res_dev took (tests,
+ * tuning; results never depend on them): out[0] = segments resolved in LDS,
+ * out[1] = segments resolved through a scratch table, out[2] = entries that
+ * lost to a later entry of their element in their segment, out[3] = bytes of
+ * the scratch tables. */
+int syzsig_poll_res_stats(syzsig_ctx* ctx, uint64_t out[4]);
+
 /* ---- pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output regions ----
  * Program p's output region (executor.h:566-604 records, the executor's shmem
  * out file) is d_out[prog_off[p] .. prog_off[p+1]); it has the calls

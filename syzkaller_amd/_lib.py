@@ -30,6 +30,9 @@ SYZSIG_COVER_TILE = 4096  # include/syzsig.h: longer segments leave the one-work
 SYZSIG_COMPS_TILE = 2048  # the same for the comparison hints' keys (comps.hip)
 SYZSIG_CORPUS_TILE = 2048  # the same for a corpus key's entries in the NewInput batch (corpus.hip)
 SYZSIG_ITEMS_TILE = 4096  # the same for a triage item's records (items.hip)
+SYZSIG_POLLRES_TILE = 4096  # a poll reply's Serial past it leaves the one-workgroup LDS table (pollres.hip)
+SYZSIG_SEG_MAXSIGNAL = 0  # syzsig_fuzzer_poll_res_dev: a reply's MaxSignal (fuzzer.go:344-347)
+SYZSIG_SEG_INPUT = 1  # ... the Signal of one of its NewInputs (fuzzer.go:348-350)
 SYZSIG_INPUT_PRESENT = 1  # a NewInput batch row that is the key's old corpus entry
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
@@ -149,6 +152,8 @@ SIGNATURES = {
                                         _P, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "syzsig_triage_items_stats": (c_int, [_P, _P]),
     "syzsig_corpus_add_inputs_dev": (c_int, [_P, _P, _P, c_uint64, _P, c_uint64, _P, _PP, _PP]),
+    "syzsig_fuzzer_poll_res_dev": (c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, _PP, _PP]),
+    "syzsig_poll_res_stats": (c_int, [_P, _P]),
     "syzsig_exec_comps_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P, _P]),
     "syzsig_comp_map_dev": (c_int, [_P, _P, c_uint64, _P, _P, _P, c_uint64, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     "syzsig_shrink_expand_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, _P, c_uint64, _P, c_uint32, _P, _P,

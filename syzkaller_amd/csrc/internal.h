@@ -140,7 +140,9 @@ enum WsSlot : int {
 	kWsSuStage2 = 37,  // comps.hip, items.hip (see kWsSuMeta)
 	kWsNiGroupCover = 38,
 	// manager poll (poll.hip) | the NewInput batch's acceptance and uploads (corpus.hip)
+	// | the fuzzer's poll reply (pollres.hip): its routing arrays and the long segments' scratch tables
 	kWsPollTargets = 39,
+	kWsPrMeta = 39,
 	kWsPollElems = 40,
 	kWsNiElems = 40,
 	kWsPollPrios = 41,
@@ -153,6 +155,7 @@ enum WsSlot : int {
 	kWsNiStageB = 44,  // acceptance: the sort keys, then the commit: cover offsets
 	kWsNiRecs = 45,
 	kWsPollTable = 46,
+	kWsPrTable = 46,
 	kWsNiEvents = 46,
 	kWsPollCounts = 47,
 	kWsNiAccepted = 47,
@@ -245,6 +248,7 @@ struct syzsig_ctx {
 	hipEvent_t ev_step[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	uint64_t ni_stats[4] = {0, 0, 0, 0};  // syzsig_new_input_stats: the last NewInput batch's paths (corpus.hip)
 	uint64_t it_stats[4] = {0, 0, 0, 0};  // syzsig_triage_items_stats: the last triage_items call's paths (items.hip)
+	uint64_t pr_stats[4] = {0, 0, 0, 0};  // syzsig_poll_res_stats: the last fuzzer_poll_res call's paths (pollres.hip)
 };
 
 struct syzsig_set {

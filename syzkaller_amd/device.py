@@ -387,6 +387,37 @@ class Device:
         if mh.value and max_signal.is_nil():
             max_signal._h = mh
 
+    def poll_res(self, seg_off, seg_kind, elems, prios, corpus_signal, max_signal):
+        """The reply to a fuzzer's poll (fuzzer.go:344-350) over a batch of
+        Serials (syzsig_fuzzer_poll_res_dev): segment s is elems / prios
+        [seg_off[s] : seg_off[s + 1]] (seg_off int64[nseg + 1]) and seg_kind[s]
+        (uint8) is SYZSIG_SEG_MAXSIGNAL (addMaxSignal, :468-475: merged into
+        max_signal) or SYZSIG_SEG_INPUT (addInputFromAnotherFuzzer, :433-460:
+        merged into corpus_signal and max_signal).  Each segment is
+        deserialized first: the last entry of an element gives its prio.
+        corpus_signal / max_signal are Signal objects; a nil one is allocated
+        when a non-empty segment reaches it."""
+        self._check_dev(seg_off, seg_kind, elems, prios)
+        nseg = seg_kind.numel()
+        if seg_off.numel() != nseg + 1 or prios.numel() != elems.numel():
+            raise ValueError("seg_off needs nseg + 1 entries, prios one per element")
+        ch = ctypes.c_void_p(corpus_signal.handle.value or 0)
+        mh = ctypes.c_void_p(max_signal.handle.value or 0)
+        check(self.L.syzsig_fuzzer_poll_res_dev(self.eng.h, _p(seg_off), _p(seg_kind), nseg, _p(elems), _p(prios),
+                                                elems.numel(), ctypes.byref(ch), ctypes.byref(mh)))
+        if ch.value and corpus_signal.is_nil():
+            corpus_signal._h = ch
+        if mh.value and max_signal.is_nil():
+            max_signal._h = mh
+
+    def poll_res_stats(self):
+        """(segments resolved in LDS, segments resolved through a scratch
+        table, entries that lost to a later entry of their element, scratch
+        bytes) of the last poll_res call (syzsig_poll_res_stats)."""
+        out = (ctypes.c_uint64 * 4)()
+        check(self.L.syzsig_poll_res_stats(self.eng.h, out))
+        return tuple(int(x) for x in out)
+
     def minimize_pred(self, item_off, elems, prios, item_flags, attempts, run_off, run_sigs, run_prio, run_errno,
                       run_exec):
         """triageInput's minimize predicate (proc.go:141-160) per item; uint8 tensor."""

@@ -21,7 +21,8 @@ from . import _lib
 from ._lib import check
 
 __all__ = ["Engine", "engine", "Signal", "Cover", "Serial", "Context", "FromRaw", "Minimize", "signal_prio",
-           "check_new_signal", "manager_poll", "manager_new_input", "new_input_stats"]
+           "check_new_signal", "manager_poll", "manager_new_input", "new_input_stats", "fuzzer_poll_res",
+           "poll_res_stats"]
 
 
 class Engine:
@@ -513,3 +514,68 @@ def new_input_stats(eng=None):
     out = np.zeros(4, dtype=np.uint64)
     check(eng.L.syzsig_new_input_stats(eng.h, _ptr(out)))
     return dict(zip(("sequential", "large_keys", "merge_passes", "large_covers"), (int(x) for x in out)))
+
+
+def fuzzer_poll_res(corpus_signal, max_signal, max_serial, new_inputs, eng=None):
+    """syz-fuzzer/fuzzer.go:344-350: the fuzzer's side of one PollRes
+    (syzsig_fuzzer_poll_res_dev).  max_serial = r.MaxSignal (a Serial, or None):
+    deserialized and merged into max_signal (addMaxSignal, :468-475).
+    new_inputs = the Signal Serial of every one of r.NewInputs, in order: each
+    is deserialized and merged into corpus_signal and max_signal
+    (addInputFromAnotherFuzzer, :433-460).  The Signals are updated in place; a
+    nil one stays nil unless a non-empty Serial reaches it."""
+    import torch  # the upload's plumbing, as in device.py
+
+    eng = eng or max_signal._e
+    sers = ([max_serial] if max_serial is not None else []) + list(new_inputs)
+    kinds = np.array([_lib.SYZSIG_SEG_MAXSIGNAL] * (max_serial is not None) + [_lib.SYZSIG_SEG_INPUT] * len(new_inputs),
+                     dtype=np.uint8)
+    K = len(sers)
+    if K == 0:
+        return
+    lens = np.array([np.asarray(s.Elems).size for s in sers], dtype=np.uint64)
+    for s in sers:
+        if np.asarray(s.Elems).size != np.asarray(s.Prios).size:
+            raise _lib.CorruptedSerial(_lib.SYZSIG_ECORRUPT, "corrupted Serial")  # signal.go:60-62
+    n = int(lens.sum())
+    # offsets, elements, prios and kinds back to back in page-locked memory: one DMA
+    o_elems = 8 * (K + 1)
+    o_prios = o_elems + 4 * n
+    o_kinds = o_prios + n
+    total = o_kinds + K
+    buf = eng.staging(total + 64)
+    off = buf[:o_elems].view(np.uint64)
+    off[0] = 0
+    np.cumsum(lens, out=off[1:])
+    if n:
+        np.concatenate([np.asarray(s.Elems, np.uint32) for s in sers], out=buf[o_elems:o_prios].view(np.uint32))
+        np.concatenate([np.asarray(s.Prios, np.int8) for s in sers], out=buf[o_prios:o_kinds].view(np.int8))
+    buf[o_kinds:total] = kinds
+    dev = torch.device("cuda", eng.device)
+    d = torch.from_numpy(buf[:total]).to(dev, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()  # the library's stream may be another one
+    base = d.data_ptr()
+    ch = ctypes.c_void_p(corpus_signal.handle.value or 0)
+    mh = ctypes.c_void_p(max_signal.handle.value or 0)
+    try:
+        check(eng.L.syzsig_fuzzer_poll_res_dev(eng.h, ctypes.c_void_p(base), ctypes.c_void_p(base + o_kinds), K,
+                                               ctypes.c_void_p(base + o_elems), ctypes.c_void_p(base + o_prios), n,
+                                               ctypes.byref(ch), ctypes.byref(mh)))
+    finally:
+        # the library allocates a nil set only on success and leaves the handles as they were on an error
+        if ch.value and corpus_signal.is_nil():
+            corpus_signal._h = ch
+        if mh.value and max_signal.is_nil():
+            max_signal._h = mh
+    del d
+
+
+def poll_res_stats(eng=None):
+    """Which paths the engine's last fuzzer_poll_res took
+    (syzsig_poll_res_stats): segments resolved in LDS, segments resolved
+    through a scratch table, entries that lost to a later entry of their
+    element, scratch bytes."""
+    eng = eng or engine()
+    out = np.zeros(4, dtype=np.uint64)
+    check(eng.L.syzsig_poll_res_stats(eng.h, _ptr(out)))
+    return tuple(int(x) for x in out)
