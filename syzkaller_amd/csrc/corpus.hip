@@ -118,12 +118,8 @@ __global__ __launch_bounds__(kNiThreads) void k_ni_commit(const uint64_t* __rest
 {
 	uint64_t ins = 0, cins = 0, ovf = 0;
 	if (blockIdx.x < ev_blocks) {
-		for (uint64_t x = blockIdx.x * (uint64_t)kNiThreads + threadIdx.x; x < nev; x += (uint64_t)ev_blocks * kNiThreads) {
-			const uint64_t w = ev[x];
-			const int rr = tbl_merge(cs, cs_bmask, (uint32_t)(w >> 32), (int8_t)((uint8_t)w ^ 0x80u));
-			ins += rr == 1;
-			ovf += rr < 0;
-		}
+		merge_events(ev, nev, blockIdx.x * (uint64_t)kNiThreads + threadIdx.x, (uint64_t)ev_blocks * kNiThreads, cs,
+		             cs_bmask, ins, ovf);
 	} else {
 		const uint32_t rb = gridDim.x - ev_blocks;  // (cover_off is relative to the uploaded covers)
 		for (uint32_t i = blockIdx.x - ev_blocks; i < nrows; i += rb) {
@@ -244,16 +240,6 @@ static int ni_upload(syzsig_ctx* ctx, int slot, const void* h, size_t bytes, voi
 	return SYZSIG_OK;
 }
 
-// Sets this call made, freed again unless it hands them out.
-struct NiFresh {
-	std::vector<syzsig_set*> sets;
-	~NiFresh()
-	{
-		for (syzsig_set* x : sets)
-			syzsig_set_free(x);
-	}
-};
-
 // one batch, as the entry point validated it
 struct NiBatch {
 	uint32_t K, nkeys;
@@ -284,7 +270,7 @@ struct NiAccept {
 	uint8_t* d_acc = nullptr;
 	// sequential: the clones the loop ran on (nullptr = still nil)
 	syzsig_set *cs = nullptr, *cv = nullptr;
-	NiFresh work;
+	OwnedSets work;
 };
 
 // The reference loop itself (manager.go:976-998), one input after the other
@@ -297,29 +283,24 @@ static int ni_accept_sequential(syzsig_ctx* ctx, const NiBatch& B, syzsig_set* c
 {
 	A->sequential = true;
 	SYZ_TRY(syzsig_set_clone(ctx, corpus_signal, &A->cs));
-	if (A->cs)
-		A->work.sets.push_back(A->cs);
+	A->work.add(A->cs);
 	SYZ_TRY(syzsig_set_clone(ctx, corpus_cover, &A->cv));
-	if (A->cv)
-		A->work.sets.push_back(A->cv);
+	A->work.add(A->cv);
 	for (uint32_t i = 0; i < B.K; i++) {
 		if (B.present(i))
 			continue;
 		const uint64_t a = B.sig_off[i], n = B.sig_len(i);
-		NiFresh tmp;  // inputSignal and the Diff, freed at the end of the iteration
-		tmp.sets.assign(2, nullptr);
-		SYZ_TRY(syzsig_deserialize(ctx, n ? B.elems + a : nullptr, n, n ? B.prios + a : nullptr, n, &tmp.sets[0]));
-		SYZ_TRY(syzsig_diff(ctx, A->cs, tmp.sets[0], &tmp.sets[1]));
-		if (syzsig_empty(tmp.sets[1]))
+		OwnedSets tmp;  // inputSignal and the Diff, freed at the end of the iteration
+		syzsig_set *in = nullptr, *diff = nullptr;
+		SYZ_TRY(syzsig_deserialize(ctx, n ? B.elems + a : nullptr, n, n ? B.prios + a : nullptr, n, &in));
+		tmp.add(in);
+		SYZ_TRY(syzsig_diff(ctx, A->cs, in, &diff));
+		tmp.add(diff);
+		if (syzsig_empty(diff))
 			continue;  // :993
-		syzsig_set* const cs0 = A->cs;
-		SYZ_TRY(syzsig_merge(ctx, &A->cs, tmp.sets[0]));  // :997
-		if (!cs0)
-			A->work.sets.push_back(A->cs);
-		syzsig_set* const cv0 = A->cv;
-		SYZ_TRY(syzsig_cover_merge(ctx, &A->cv, B.cov_len(i) ? B.cover + B.cover_off[i] : nullptr, B.cov_len(i)));  // :998
-		if (!cv0)
-			A->work.sets.push_back(A->cv);
+		SYZ_TRY(merge_into(ctx, A->work, &A->cs, in));  // :997
+		SYZ_TRY(cover_merge_into(ctx, A->work, &A->cv, B.cov_len(i) ? B.cover + B.cover_off[i] : nullptr,
+		                         B.cov_len(i)));  // :998
 		acc[i] = 1;
 	}
 	return SYZSIG_OK;
@@ -573,19 +554,9 @@ static int ni_commit(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, NiAc
                      syzsig_set** corpus_cover)
 {
 	if (A->sequential) {
-		// corpusSignal and corpusCover keep their handles (callers hold them):
-		// the clones' contents move into them, as poll_sequential does
-		syzsig_set** dst[2] = {corpus_signal, corpus_cover};
-		syzsig_set* cl[2] = {A->cs, A->cv};
-		A->work.sets.clear();
-		for (int x = 0; x < 2; x++) {
-			if (*dst[x] && cl[x]) {
-				std::swap(**dst[x], *cl[x]);
-				syzsig_set_free(cl[x]);  // (the old storage)
-			} else if (cl[x]) {
-				*dst[x] = cl[x];  // allocated by the first accepted input
-			}
-		}
+		A->work.release();
+		swap_in(corpus_signal, A->cs);
+		swap_in(corpus_cover, A->cv);
 		return SYZSIG_OK;
 	}
 	uint64_t cacc = 0;
@@ -598,18 +569,9 @@ static int ni_commit(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, NiAc
 	if (!any)
 		return SYZSIG_OK;  // nil sets stay nil
 	const hipStream_t s = ctx->stream;
-	NiFresh fresh;
-	syzsig_set *cs = *corpus_signal, *cv = *corpus_cover;
-	if (!cs) {
-		SYZ_TRY(syzsig_set_make(ctx, A->E, &cs));  // Merge allocates a nil receiver (signal.go:121-125)
-		fresh.sets.push_back(cs);
-	}
-	SYZ_TRY(set_reserve(cs, A->E));
-	if (!cv) {
-		SYZ_TRY(syzsig_set_make(ctx, cacc, &cv));  // cover.go:9-18: even for an empty cover
-		fresh.sets.push_back(cv);
-	}
-	SYZ_TRY(set_reserve(cv, cacc));
+	Receiver cs, cv;
+	SYZ_TRY(cs.open(ctx, corpus_signal, A->E));  // Merge allocates a nil receiver (signal.go:121-125)
+	SYZ_TRY(cv.open(ctx, corpus_cover, cacc));   // cover.go:9-18: even for an empty cover
 	void *dfl, *dco;
 	SYZ_TRY(ni_upload(ctx, kWsNiStageA, B.flags, B.K, &dfl));
 	std::vector<uint64_t> co((size_t)B.K + 1);
@@ -618,18 +580,12 @@ static int ni_commit(syzsig_ctx* ctx, const NiBatch& B, const uint8_t* acc, NiAc
 	SYZ_TRY(ni_upload(ctx, kWsNiStageB, co.data(), ((size_t)B.K + 1) * 8, &dco));
 	SYZ_TRY(counters_reset(ctx));
 	const uint32_t eb = (uint32_t)grid_for(A->E, kNiThreads, 8192), rb = cacc ? (uint32_t)grid_cap(B.K, kNiMaxGrid) : 0;
-	k_ni_commit<<<eb + rb, kNiThreads, 0, s>>>(A->d_ev, A->E, eb, cs->slots, cs->nbuckets - 1, A->d_acc,
-	                                           (const uint8_t*)dfl, (const uint64_t*)dco, B.K, B.d_cover, cv->slots,
-	                                           cv->nbuckets - 1, ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
-	SYZ_TRY(counters_fetch(ctx));  // (synchronizes: co is consumed)
-	if (ctx->h_cnt[kCntOverflow])
-		return fail(SYZSIG_EIO, "manager_new_input_batch: table overflow after reserve (internal error)");
-	fresh.sets.clear();
-	cs->len += ctx->h_cnt[kCntInserted];
-	cv->len += ctx->h_cnt[kNiCovIns];
-	*corpus_signal = cs;
-	*corpus_cover = cv;
+	k_ni_commit<<<eb + rb, kNiThreads, 0, s>>>(A->d_ev, A->E, eb, cs.slots(), cs.bmask(), A->d_acc,
+	                                           (const uint8_t*)dfl, (const uint64_t*)dco, B.K, B.d_cover, cv.slots(),
+	                                           cv.bmask(), ctx->d_cnt);
+	SYZ_TRY(commit_tail(ctx, "manager_new_input_batch"));  // (synchronizes: co is consumed)
+	cs.commit(ctx->h_cnt[kCntInserted]);
+	cv.commit(ctx->h_cnt[kNiCovIns]);
 	return SYZSIG_OK;
 }
 
@@ -639,11 +595,7 @@ using namespace syz;
 
 extern "C" int syzsig_new_input_stats(syzsig_ctx* ctx, uint64_t out[4])
 {
-	SYZ_LOCK(ctx);
-	if (!ctx || !out)
-		return fail(SYZSIG_EINVAL, "new_input_stats: NULL argument");
-	std::copy(ctx->ni_stats, ctx->ni_stats + 4, out);
-	return SYZSIG_OK;
+	return stats_copy(ctx, &syzsig_ctx::ni_stats, out, "new_input_stats");
 }
 
 extern "C" int syzsig_manager_new_input_batch(syzsig_ctx* ctx, syzsig_set** corpus_signal, syzsig_set** corpus_cover,

@@ -437,7 +437,32 @@ inline int grid_for(uint64_t n, int block, int max_blocks = 2048)
 	return (int)g;
 }
 
+// The tail of a launch that inserted into tables with room reserved: the
+// launch error, the counters (synchronizes), and an overflow that the
+// reservation rules out.  `who` = the entry point, for the message.
+inline int commit_tail(syzsig_ctx* ctx, const char* who)
+{
+	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(counters_fetch(ctx));
+	if (ctx->h_cnt[kCntOverflow])
+		return fail(SYZSIG_EIO, std::string(who) + ": table overflow after reserve (internal error)");
+	return SYZSIG_OK;
+}
+
+// the body of the syzsig_*_stats entry points: the last call's paths
+inline int stats_copy(syzsig_ctx* ctx, uint64_t (syzsig_ctx::*stats)[4], uint64_t* out, const char* who)
+{
+	SYZ_LOCK(ctx);
+	if (!ctx || !out)
+		return fail(SYZSIG_EINVAL, std::string(who) + ": NULL argument");
+	for (int i = 0; i < 4; i++)
+		out[i] = (ctx->*stats)[i];
+	return SYZSIG_OK;
+}
+
 }  // namespace syz
+
+#include "receiver.h"
 
 // ---------------------------------------------------------------------------
 // device primitives
@@ -502,15 +527,23 @@ __device__ __forceinline__ uint64_t home_bucket(uint32_t key, uint64_t bmask)
 	return ((uint64_t)fmix32(key) * (bmask + 1)) >> 32;
 }
 
+// The table primitives below have one body each; kPreloaded says whether the
+// caller passes the home bucket already loaded (B = load_bucket of
+// home_bucket(key)), so that a thread can issue the home-bucket loads of several
+// tables or keys before it walks any of them.  A stale B is safe for the same
+// reason a fresh one is: slots only go EMPTY -> key, and the CAS sees the
+// current word.
+
 // Lookup.  Returns the slot index, or -1 if absent (first empty slot reached:
 // slots only ever go EMPTY -> key, so occupied slots form a prefix of every
 // probe sequence).
-__device__ __forceinline__ int64_t tbl_lookup(const uint64_t* __restrict__ slots, uint64_t bmask, uint32_t key,
-                                              uint64_t& val)
+template <bool kPreloaded>
+__device__ __forceinline__ int64_t tbl_lookup_impl(const uint64_t* __restrict__ slots, uint64_t bmask, uint32_t key,
+                                                   uint64_t& val, const Bucket& B0)
 {
 	uint64_t b = home_bucket(key, bmask);
 	for (uint64_t n = 0; n <= bmask; n++) {
-		Bucket B = load_bucket(slots + (b << kBucketShift));
+		const Bucket B = kPreloaded && n == 0 ? B0 : load_bucket(slots + (b << kBucketShift));
 #pragma unroll
 		for (int i = 0; i < (int)kBucketSlots; i++) {
 			if (B.s[i] == kSlotEmpty)
@@ -525,71 +558,29 @@ __device__ __forceinline__ int64_t tbl_lookup(const uint64_t* __restrict__ slots
 	return -1;
 }
 
-// tbl_lookup with the home bucket already loaded (B = load_bucket of
-// home_bucket(key)), so that a thread can issue several tables' home-bucket
-// loads before it waits for any.
+__device__ __forceinline__ int64_t tbl_lookup(const uint64_t* __restrict__ slots, uint64_t bmask, uint32_t key,
+                                              uint64_t& val)
+{
+	return tbl_lookup_impl<false>(slots, bmask, key, val, Bucket{});
+}
+
 __device__ __forceinline__ int64_t tbl_lookup_from(const uint64_t* __restrict__ slots, uint64_t bmask, uint32_t key,
                                                    uint64_t& val, Bucket B)
 {
-	uint64_t b = home_bucket(key, bmask);
-	for (uint64_t n = 0; n <= bmask; n++) {
-		if (n)
-			B = load_bucket(slots + (b << kBucketShift));
-#pragma unroll
-		for (int i = 0; i < (int)kBucketSlots; i++) {
-			if (B.s[i] == kSlotEmpty)
-				return -1;
-			if (slot_key(B.s[i]) == key) {
-				val = B.s[i];
-				return (int64_t)((b << kBucketShift) + i);
-			}
-		}
-		b = (b + 1) & bmask;
-	}
-	return -1;
+	return tbl_lookup_impl<true>(slots, bmask, key, val, B);
 }
 
 // Find `key`, inserting `ins` (a slot word for `key`) at the first empty slot
 // if absent.  old = previous word (0 when this call inserted).  Returns -1
 // when max_probe buckets were scanned without success (overflow).
-__device__ __forceinline__ int64_t tbl_find_or_insert(uint64_t* slots, uint64_t bmask, uint32_t key, uint64_t ins,
-                                                      uint64_t& old, uint64_t max_probe)
+template <bool kPreloaded>
+__device__ __forceinline__ int64_t tbl_find_or_insert_impl(uint64_t* slots, uint64_t bmask, uint32_t key, uint64_t ins,
+                                                           uint64_t& old, uint64_t max_probe, Bucket B)
 {
 	uint64_t b = home_bucket(key, bmask);
 	for (uint64_t n = 0; n < max_probe; n++) {
 		uint64_t* bp = slots + (b << kBucketShift);
-		Bucket B = load_bucket(bp);
-#pragma unroll
-		for (int i = 0; i < (int)kBucketSlots; i++) {
-			uint64_t s = B.s[i];
-			if (s == kSlotEmpty) {
-				s = atomicCAS(reinterpret_cast<unsigned long long*>(bp + i), 0ull, (unsigned long long)ins);
-				if (s == kSlotEmpty) {
-					old = 0;
-					return (int64_t)((b << kBucketShift) + i);
-				}
-			}
-			if (slot_key(s) == key) {
-				old = s;
-				return (int64_t)((b << kBucketShift) + i);
-			}
-		}
-		b = (b + 1) & bmask;
-	}
-	return -1;
-}
-
-// tbl_find_or_insert with the home bucket already loaded (B = load_bucket of
-// home_bucket(key)): a thread can issue the home-bucket loads of several keys
-// before it walks any of them.  A stale B is safe for the same reason a fresh
-// one is: slots only go EMPTY -> key, and the CAS sees the current word.
-__device__ __forceinline__ int64_t tbl_find_or_insert_from(uint64_t* slots, uint64_t bmask, uint32_t key,
-                                                           uint64_t ins, uint64_t& old, uint64_t max_probe, Bucket B)
-{
-	uint64_t b = home_bucket(key, bmask);
-	for (uint64_t n = 0; n < max_probe; n++) {
-		uint64_t* bp = slots + (b << kBucketShift);
-		if (n)
+		if (!kPreloaded || n)
 			B = load_bucket(bp);
 #pragma unroll
 		for (int i = 0; i < (int)kBucketSlots; i++) {
@@ -611,6 +602,18 @@ __device__ __forceinline__ int64_t tbl_find_or_insert_from(uint64_t* slots, uint
 	return -1;
 }
 
+__device__ __forceinline__ int64_t tbl_find_or_insert(uint64_t* slots, uint64_t bmask, uint32_t key, uint64_t ins,
+                                                      uint64_t& old, uint64_t max_probe)
+{
+	return tbl_find_or_insert_impl<false>(slots, bmask, key, ins, old, max_probe, Bucket{});
+}
+
+__device__ __forceinline__ int64_t tbl_find_or_insert_from(uint64_t* slots, uint64_t bmask, uint32_t key,
+                                                           uint64_t ins, uint64_t& old, uint64_t max_probe, Bucket B)
+{
+	return tbl_find_or_insert_impl<true>(slots, bmask, key, ins, old, max_probe, B);
+}
+
 // Probe bound of an insert: the whole table.  The set operations reserve room
 // first (set_reserve*: below load 1), so an empty slot exists and an insert
 // cannot fail however long its chain is -- also when every key shares one home
@@ -621,10 +624,11 @@ __device__ __forceinline__ uint64_t max_probe_for(uint64_t bmask)
 }
 
 // Insert-or-max (Merge rule).  Returns 1 if inserted, 0 otherwise; -1 overflow.
-__device__ __forceinline__ int tbl_merge(uint64_t* slots, uint64_t bmask, uint32_t key, int8_t prio)
+template <bool kPreloaded>
+__device__ __forceinline__ int tbl_merge_impl(uint64_t* slots, uint64_t bmask, uint32_t key, int8_t prio, Bucket B)
 {
 	uint64_t v = make_slot(key, prio), old;
-	int64_t idx = tbl_find_or_insert(slots, bmask, key, v, old, max_probe_for(bmask));
+	int64_t idx = tbl_find_or_insert_impl<kPreloaded>(slots, bmask, key, v, old, max_probe_for(bmask), B);
 	if (idx < 0)
 		return -1;
 	if (old == 0)
@@ -634,18 +638,51 @@ __device__ __forceinline__ int tbl_merge(uint64_t* slots, uint64_t bmask, uint32
 	return 0;
 }
 
-// tbl_merge from a preloaded home bucket (see tbl_find_or_insert_from).
+__device__ __forceinline__ int tbl_merge(uint64_t* slots, uint64_t bmask, uint32_t key, int8_t prio)
+{
+	return tbl_merge_impl<false>(slots, bmask, key, prio, Bucket{});
+}
+
 __device__ __forceinline__ int tbl_merge_from(uint64_t* slots, uint64_t bmask, uint32_t key, int8_t prio, Bucket B)
 {
-	uint64_t v = make_slot(key, prio), old;
-	int64_t idx = tbl_find_or_insert_from(slots, bmask, key, v, old, max_probe_for(bmask), B);
-	if (idx < 0)
-		return -1;
-	if (old == 0)
-		return 1;
-	if (old < v)
-		atomicMax(reinterpret_cast<unsigned long long*>(slots + idx), (unsigned long long)v);
-	return 0;
+	return tbl_merge_impl<true>(slots, bmask, key, prio, B);
+}
+
+// corpusSignal.Merge and maxSignal.Merge of one (e, p) (fuzzer.go:456-457), or
+// maxSignal's alone (:474) when !input: both tables' home buckets are loaded
+// before either chain is walked.  Adds to the caller's counts.
+__device__ __forceinline__ void tbl_merge2(uint64_t* corpus, uint64_t c_bmask, uint64_t* max, uint64_t m_bmask,
+                                           uint32_t e, int8_t p, bool input, uint64_t& ins_c, uint64_t& ins_m,
+                                           uint64_t& ovf)
+{
+	Bucket bc = {};
+	if (input)
+		bc = load_bucket(corpus + (home_bucket(e, c_bmask) << kBucketShift));
+	const Bucket bm = load_bucket(max + (home_bucket(e, m_bmask) << kBucketShift));
+	if (input) {
+		const int rc = tbl_merge_from(corpus, c_bmask, e, p, bc);
+		ins_c += rc == 1;
+		ovf += rc < 0;
+	}
+	const int rm = tbl_merge_from(max, m_bmask, e, p, bm);
+	ins_m += rm == 1;
+	ovf += rm < 0;
+}
+
+// Merge of a batch's events (e << 32 | ... | prio ^ 0x80 in the low byte: poll.hip,
+// corpus.hip) into one table, max-merged: an element's last event carries its
+// final max, the earlier ones are below it.  This thread takes ev[first],
+// ev[first + stride], ...
+__device__ __forceinline__ void merge_events(const uint64_t* __restrict__ ev, uint64_t n, uint64_t first,
+                                             uint64_t stride, uint64_t* tbl, uint64_t bmask, uint64_t& ins,
+                                             uint64_t& ovf)
+{
+	for (uint64_t x = first; x < n; x += stride) {
+		const uint64_t w = ev[x];
+		const int rr = tbl_merge(tbl, bmask, (uint32_t)(w >> 32), (int8_t)((uint8_t)w ^ 0x80u));
+		ins += rr == 1;
+		ovf += rr < 0;
+	}
 }
 
 }  // namespace syz

@@ -205,9 +205,8 @@ __global__ __launch_bounds__(kItThreads) void k_it_kept(const uint64_t* __restri
 	block_count(&cnt[kSuTotal], tot);
 }
 
-// fuzzer.go:456-457 for every kept item: both tables' home buckets are loaded
-// before either chain is walked.  Max-merge commutes, so the order the
-// workgroups run in does not show.
+// fuzzer.go:456-457 for every kept item (tbl_merge2).  Max-merge commutes, so
+// the order the workgroups run in does not show.
 __global__ __launch_bounds__(kItThreads) void k_it_commit(const uint64_t* __restrict__ input_off,
                                                           const uint32_t* __restrict__ elems,
                                                           const int8_t* __restrict__ item_prio, uint64_t nitems,
@@ -221,15 +220,8 @@ __global__ __launch_bounds__(kItThreads) void k_it_commit(const uint64_t* __rest
 			continue;
 		const uint64_t a = input_off[i], b = input_off[i + 1];
 		const int8_t p = item_prio[i];
-		for (uint64_t j = a + threadIdx.x; j < b; j += kItThreads) {
-			const uint32_t e = elems[j];
-			const Bucket bc = load_bucket(corpus + (home_bucket(e, c_bmask) << kBucketShift));
-			const Bucket bm = load_bucket(max + (home_bucket(e, m_bmask) << kBucketShift));
-			const int rc = tbl_merge_from(corpus, c_bmask, e, p, bc), rm = tbl_merge_from(max, m_bmask, e, p, bm);
-			ins_c += rc == 1;
-			ins_m += rm == 1;
-			ovf += (rc < 0) + (rm < 0);
-		}
+		for (uint64_t j = a + threadIdx.x; j < b; j += kItThreads)
+			tbl_merge2(corpus, c_bmask, max, m_bmask, elems[j], p, true, ins_c, ins_m, ovf);
 	}
 	block_count(&cnt[kCntInserted], ins_c);
 	block_count(&cnt[kCntAux], ins_m);
@@ -358,11 +350,7 @@ extern "C" int syzsig_triage_items_dev(syzsig_ctx* ctx, const uint32_t* d_sigs, 
 
 extern "C" int syzsig_triage_items_stats(syzsig_ctx* ctx, uint64_t out[4])
 {
-	SYZ_LOCK(ctx);
-	if (!ctx || !out)
-		return fail(SYZSIG_EINVAL, "triage_items_stats: NULL argument");
-	std::copy(ctx->it_stats, ctx->it_stats + 4, out);
-	return SYZSIG_OK;
+	return stats_copy(ctx, &syzsig_ctx::it_stats, out, "triage_items_stats");
 }
 
 extern "C" int syzsig_corpus_add_inputs_dev(syzsig_ctx* ctx, const uint64_t* d_input_off, const uint32_t* d_input_elems,
@@ -393,34 +381,15 @@ extern "C" int syzsig_corpus_add_inputs_dev(syzsig_ctx* ctx, const uint64_t* d_i
 		return SYZSIG_OK;  // nothing kept, or only empty signs: nil receivers stay nil (fuzzer.go:454)
 	// room in both tables first (a nil receiver: its table, signal.go:121-125);
 	// nothing below the reservations can fail short of the device itself
-	syzsig_set *cs = *corpus_signal, *ms = *max_signal, *new_cs = nullptr, *new_ms = nullptr;
-	int rc = cs ? set_reserve(cs, total) : set_alloc(ctx, buckets_for(total), &new_cs);
-	if (rc == SYZSIG_OK)
-		rc = ms ? set_reserve(ms, total) : set_alloc(ctx, buckets_for(total), &new_ms);
-	if (rc == SYZSIG_OK)
-		rc = counters_reset(ctx);
-	if (rc != SYZSIG_OK) {
-		syzsig_set_free(new_cs);
-		syzsig_set_free(new_ms);
-		return rc;
-	}
-	cs = cs ? cs : new_cs;
-	ms = ms ? ms : new_ms;
+	Receiver cs, ms;
+	SYZ_TRY(cs.open(ctx, corpus_signal, total));
+	SYZ_TRY(ms.open(ctx, max_signal, total));
+	SYZ_TRY(counters_reset(ctx));
 	k_it_commit<<<grid_cap(n_items, 1u << 16), kItThreads, 0, s>>>(d_input_off, d_input_elems, d_item_prio, n_items,
-	                                                               d_item_keep, cs->slots, cs->nbuckets - 1, ms->slots,
-	                                                               ms->nbuckets - 1, ctx->d_cnt);
-	const hipError_t e = hipGetLastError();
-	rc = e == hipSuccess ? counters_fetch(ctx) : hip_fail(e, "k_it_commit", __FILE__, __LINE__);
-	if (rc == SYZSIG_OK && ctx->h_cnt[kCntOverflow])
-		rc = fail(SYZSIG_EIO, "corpus_add_inputs: internal: a reserved table overflowed");
-	if (rc != SYZSIG_OK) {
-		syzsig_set_free(new_cs);
-		syzsig_set_free(new_ms);
-		return rc;
-	}
-	cs->len += ctx->h_cnt[kCntInserted];
-	ms->len += ctx->h_cnt[kCntAux];
-	*corpus_signal = cs;
-	*max_signal = ms;
+	                                                               d_item_keep, cs.slots(), cs.bmask(), ms.slots(),
+	                                                               ms.bmask(), ctx->d_cnt);
+	SYZ_TRY(commit_tail(ctx, "corpus_add_inputs"));
+	cs.commit(ctx->h_cnt[kCntInserted]);
+	ms.commit(ctx->h_cnt[kCntAux]);
 	return SYZSIG_OK;
 }

@@ -117,12 +117,8 @@ __global__ void k_poll_commit(const uint64_t* __restrict__ ev, uint64_t n, uint6
                               unsigned long long* ctr)
 {
 	uint64_t ins = 0, ovf = 0;
-	for (uint64_t x = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; x < n; x += (uint64_t)gridDim.x * blockDim.x) {
-		const uint64_t w = ev[x];
-		const int rr = tbl_merge(ms, ms_bmask, (uint32_t)(w >> 32), (int8_t)((uint8_t)w ^ 0x80u));
-		ins += rr == 1;
-		ovf += rr < 0;
-	}
+	merge_events(ev, n, blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x, ms, ms_bmask,
+	             ins, ovf);
 	block_count(&ctr[kCntInserted], ins);
 	block_count(&ctr[kCntOverflow], ovf);
 }
@@ -223,16 +219,6 @@ __global__ __launch_bounds__(256) void k_poll_scatter(const uint64_t* __restrict
 
 using namespace syz;
 
-// Sets this call made, freed again if it fails before the commit.
-struct PollFresh {
-	std::vector<syzsig_set*> sets;
-	~PollFresh()
-	{
-		for (syzsig_set* x : sets)
-			syzsig_set_free(x);
-	}
-};
-
 // The reference loop itself (manager.go:1027-1052), one poll after the other
 // over the set ops: the exact path for a batch whose entries crowd one element
 // partition past kRpCap (a hot element polled thousands of times).
@@ -247,42 +233,31 @@ static int poll_sequential(syzsig_ctx* ctx, syzsig_set** max_signal, syzsig_set*
 	// (the set ops below record the context's own events: this path's
 	// last_ms is host wall time over the loop, the stream drained at its end)
 	const auto t0 = std::chrono::steady_clock::now();
-	PollFresh work;  // clones and replies, freed unless the loop completes
+	OwnedSets work;  // clones and replies, freed unless the loop completes
 	syzsig_set* ms = nullptr;
 	SYZ_TRY(syzsig_set_clone(ctx, *max_signal, &ms));
-	if (ms)
-		work.sets.push_back(ms);
+	work.add(ms);
 	std::vector<syzsig_set*> nm(nfuzzers, nullptr), rep(npolls, nullptr);
 	for (uint32_t g = 0; g < nfuzzers; g++) {
 		SYZ_TRY(syzsig_set_clone(ctx, new_max[g], &nm[g]));
-		if (nm[g])
-			work.sets.push_back(nm[g]);
+		work.add(nm[g]);
 	}
 	for (uint32_t i = 0; i < npolls; i++) {
 		if ((ctx->agg_dbg & SYZSIG_DEBUG_POLL_FAIL) && i + 1 == npolls && i > 0)
 			return fail(SYZSIG_EIO, "manager_poll_batch: injected failure (SYZSIG_DEBUG_POLL_FAIL)");
 		const uint32_t f = poll_fuzzer[i];
 		const uint64_t a = poll_off[i], z = poll_off[i + 1];
-		syzsig_set* d = nullptr;
+		OwnedSets tmp;  // the poll's Signal and its newMax, freed at the end of the iteration
+		syzsig_set *d = nullptr, *nw = nullptr;
 		SYZ_TRY(syzsig_deserialize(ctx, elems + a, z - a, prios + a, z - a, &d));
-		PollFresh nw;  // newMax of this poll, freed at the end of the iteration
-		nw.sets.push_back(nullptr);
-		const int rc = syzsig_diff(ctx, ms, d, &nw.sets[0]);
-		syzsig_set_free(d);
-		SYZ_TRY(rc);
-		if (!syzsig_empty(nw.sets[0])) {
-			syzsig_set* const ms0 = ms;
-			SYZ_TRY(syzsig_merge(ctx, &ms, nw.sets[0]));
-			if (!ms0)
-				work.sets.push_back(ms);  // Merge allocated a nil maxSignal
-			for (uint32_t g = 0; g < nfuzzers; g++) {
-				if (g == f)
-					continue;
-				syzsig_set* const n0 = nm[g];
-				SYZ_TRY(syzsig_merge(ctx, &nm[g], nw.sets[0]));
-				if (!n0)
-					work.sets.push_back(nm[g]);
-			}
+		tmp.add(d);
+		SYZ_TRY(syzsig_diff(ctx, ms, d, &nw));
+		tmp.add(nw);
+		if (!syzsig_empty(nw)) {
+			SYZ_TRY(merge_into(ctx, work, &ms, nw));  // (Merge allocates a nil maxSignal)
+			for (uint32_t g = 0; g < nfuzzers; g++)
+				if (g != f)
+					SYZ_TRY(merge_into(ctx, work, &nm[g], nw));
 		}
 		if (!syzsig_empty(nm[f])) {  // the reply takes the fuzzer's set (the clone is in work.sets)
 			rep[i] = nm[f];
@@ -293,13 +268,8 @@ static int poll_sequential(syzsig_ctx* ctx, syzsig_set** max_signal, syzsig_set*
 	// it: the batched path merges in place too), so the clone's contents move
 	// into it; the fuzzers' newMaxSignal handles are replaced, as the batched
 	// path replaces a polled fuzzer's.
-	work.sets.clear();
-	if (*max_signal) {
-		std::swap(**max_signal, *ms);
-		syzsig_set_free(ms);  // (the old storage)
-	} else {
-		*max_signal = ms;  // nil, or allocated by a Merge
-	}
+	work.release();
+	swap_in(max_signal, ms);
 	for (uint32_t g = 0; g < nfuzzers; g++) {
 		syzsig_set_free(new_max[g]);
 		new_max[g] = nm[g];
@@ -351,17 +321,12 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 		last[poll_fuzzer[i]] = i;
 	}
 	// Nothing the caller can see changes until every set is made and sized:
-	// sets made here are freed again on an early return (PollFresh), and
+	// sets made here are freed again on an early return (OwnedSets, Receiver), and
 	// maxSignal, the fuzzers' sets and the replies are written only by the
 	// commit at the end, whose only failure is an internal overflow.
-	PollFresh fresh;
-	syzsig_set* ms = *max_signal;
-	const bool fresh_ms = !ms;  // Merge allocates a nil maxSignal only for a non-empty newMax
-	if (fresh_ms) {
-		SYZ_TRY(syzsig_set_make(ctx, n, &ms));
-		fresh.sets.push_back(ms);
-	}
-	SYZ_TRY(set_reserve(ms, n));  // (a growth keeps the contents)
+	OwnedSets fresh;
+	Receiver ms;  // (Merge allocates a nil maxSignal only for a non-empty newMax: committed only with events)
+	SYZ_TRY(ms.open(ctx, max_signal, n));
 	// uploads and scratch: entries, their grouping input, events, the target table
 	void *de, *dp, *drp, *dx, *dev, *dnext;
 	SYZ_TRY(ws_get(ctx, kWsPollElems, n * 4 + 64, &de));
@@ -391,7 +356,7 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 		uint32_t pbits;
 		SYZ_TRY(rp_group(ctx, (const uint64_t*)dx, n, &keys, &base, &pbits, ctx->d_cnt));  // (zeroes the counters)
 		k_poll_part_walk<<<1u << pbits, kSuThreads, 0, s>>>(keys, base, pbits, (const uint32_t*)drp, (const int8_t*)dp,
-		                                                    ms->slots, ms->nbuckets - 1, (uint64_t*)dev, n, nev,
+		                                                    ms.slots(), ms.bmask(), (uint64_t*)dev, n, nev,
 		                                                    ctx->d_cnt);
 		SYZ_HIP(hipGetLastError());
 	}
@@ -399,9 +364,7 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 	if (ctx->h_cnt[kCntSpill]) {
 		// an element partition past the LDS capacity: nothing was touched; the
 		// reference loop instead (a fresh maxSignal made above is dropped again)
-		fresh.sets.clear();
-		if (fresh_ms)
-			syzsig_set_free(ms);
+		ms.drop();
 		return poll_sequential(ctx, max_signal, new_max, poll_fuzzer, poll_off, elems, prios, npolls, nfuzzers,
 		                       replies);
 	}
@@ -445,7 +408,7 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 			SYZ_TRY(set_reserve(tset[t], hc[t]));
 		} else {
 			SYZ_TRY(syzsig_set_make(ctx, hc[t], &tset[t]));
-			fresh.sets.push_back(tset[t]);
+			fresh.add(tset[t]);
 		}
 		tg[t] = PollTarget{tset[t]->slots, tset[t]->nbuckets - 1};
 	}
@@ -456,23 +419,17 @@ extern "C" int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signa
 	// (the event count is passed by value: the counter reset clears *nev)
 	SYZ_TRY(counters_reset(ctx));
 	if (E)
-		k_poll_commit<<<grid_for(E, 256, 8192), 256, 0, s>>>((const uint64_t*)dev, E, ms->slots, ms->nbuckets - 1,
+		k_poll_commit<<<grid_for(E, 256, 8192), 256, 0, s>>>((const uint64_t*)dev, E, ms.slots(), ms.bmask(),
 		                                                     ctx->d_cnt);
 	k_poll_scatter<<<grid_for(C, 256, 2048), 256, 0, s>>>((const uint64_t*)dT, C, (const PollTarget*)dtg, tins, K + F,
 	                                                      ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
 	std::vector<unsigned int> hi((uint64_t)K + F);
 	SYZ_HIP(hipMemcpyAsync(hi.data(), tins, ((uint64_t)K + F) * 4, hipMemcpyDeviceToHost, s));
 	SYZ_TRY(su_time_end(ctx));
-	SYZ_TRY(counters_fetch(ctx));  // (synchronizes: hi and tg are consumed)
-	if (ctx->h_cnt[kCntOverflow])
-		return fail(SYZSIG_EIO, "manager_poll_batch: table overflow after reserve (internal error)");
-	fresh.sets.clear();  // everything made here is handed out now
-	ms->len += ctx->h_cnt[kCntInserted];
-	if (fresh_ms && !E)
-		syzsig_set_free(ms);  // nothing merged: maxSignal stays nil
-	else
-		*max_signal = ms;
+	SYZ_TRY(commit_tail(ctx, "manager_poll_batch"));  // (synchronizes: hi and tg are consumed)
+	fresh.release();  // everything made here is handed out now
+	if (E)
+		ms.commit(ctx->h_cnt[kCntInserted]);  // (nothing merged: a nil maxSignal stays nil)
 	for (uint32_t g = 0; g < F; g++) {
 		if (last[g] < K) {  // polled: the old set went into a reply; the final one is new (or nil)
 			syzsig_set_free(new_max[g]);

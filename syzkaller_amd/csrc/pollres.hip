@@ -108,26 +108,6 @@ __global__ __launch_bounds__(kSuThreads) void k_pr_route(const uint64_t* __restr
 	block_count(&cnt[kPrTotC], tc);
 }
 
-// fuzzer.go:456-457 (an INPUT segment) or :474 for one winner: both tables'
-// home buckets are loaded before either chain is walked
-__device__ __forceinline__ void pr_merge(uint32_t e, int8_t p, bool input, uint64_t* corpus, uint64_t c_bmask,
-                                         uint64_t* max, uint64_t m_bmask, uint64_t& ins_c, uint64_t& ins_m,
-                                         uint64_t& ovf)
-{
-	Bucket bc = {};
-	if (input)
-		bc = load_bucket(corpus + (home_bucket(e, c_bmask) << kBucketShift));
-	const Bucket bm = load_bucket(max + (home_bucket(e, m_bmask) << kBucketShift));
-	if (input) {
-		const int rc = tbl_merge_from(corpus, c_bmask, e, p, bc);
-		ins_c += rc == 1;
-		ovf += rc < 0;
-	}
-	const int rm = tbl_merge_from(max, m_bmask, e, p, bm);
-	ins_m += rm == 1;
-	ovf += rm < 0;
-}
-
 // home slot of an element in k_pr_short's LDS table (tests/pollres_keys.py restates it)
 __device__ __forceinline__ uint32_t pr_lds_home(uint32_t e)
 {
@@ -211,7 +191,7 @@ __global__ __launch_bounds__(kPrThreads) void k_pr_short(const uint64_t* __restr
 					losers++;
 					continue;
 				}
-				pr_merge(e[k], prios[a + i], input, corpus, c_bmask, max, m_bmask, ins_c, ins_m, ovf);
+				tbl_merge2(corpus, c_bmask, max, m_bmask, e[k], prios[a + i], input, ins_c, ins_m, ovf);
 			}
 		}
 		__syncthreads();  // the next segment clears the table
@@ -293,7 +273,7 @@ __global__ __launch_bounds__(kSuThreads) void k_pr_long_commit(
 				losers++;
 				continue;
 			}
-			pr_merge(e, prios[a + i], input, corpus, c_bmask, max, m_bmask, ins_c, ins_m, ovf);
+			tbl_merge2(corpus, c_bmask, max, m_bmask, e, prios[a + i], input, ins_c, ins_m, ovf);
 		}
 	}
 	block_count(&cnt[kPrInsC], ins_c);
@@ -338,7 +318,7 @@ int pr_route(syzsig_ctx* ctx, const PrArgs& A, const PrMeta& M, const uint8_t* f
 
 // enqueues the long path over the routed segments; tab = nbuckets zeroed buckets
 int pr_long(syzsig_ctx* ctx, const PrArgs& A, const PrMeta& M, uint64_t nchunks, uint64_t nbuckets, uint64_t* tab,
-            syzsig_set* cs, syzsig_set* ms)
+            const Receiver& cs, const Receiver& ms)
 {
 	const hipStream_t s = ctx->stream;
 	SYZ_HIP(hipMemsetAsync(tab, 0, nbuckets * kBucketSlots * sizeof(uint64_t), s));
@@ -346,8 +326,7 @@ int pr_long(syzsig_ctx* ctx, const PrArgs& A, const PrMeta& M, uint64_t nchunks,
 	                                                         M.tab_off, M.nbk, tab, ctx->d_cnt);
 	k_pr_long_commit<<<grid_cap(nchunks), kSuThreads, 0, s>>>(
 	    A.seg_off, A.seg_kind, A.elems, A.prios, A.nseg, M.chunk_off, nchunks, M.tab_off, M.nbk, tab,
-	    cs ? cs->slots : nullptr, cs ? cs->nbuckets - 1 : 0, ms->slots, ms->nbuckets - 1, ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
+	    cs.slots(), cs.bmask(), ms.slots(), ms.bmask(), ctx->d_cnt);
 	return SYZSIG_OK;
 }
 
@@ -405,47 +384,21 @@ extern "C" int syzsig_fuzzer_poll_res_dev(syzsig_ctx* ctx, const uint64_t* d_seg
 	void* tab = nullptr;
 	if (n_long)
 		SYZ_TRY(ws_get(ctx, kWsPrTable, nbuckets * kBucketSlots * sizeof(uint64_t), &tab));
-	syzsig_set *cs = *corpus_signal, *ms = *max_signal, *new_cs = nullptr, *new_ms = nullptr;
-	int rc = SYZSIG_OK;
-	if (tot_c)
-		rc = cs ? set_reserve(cs, tot_c) : set_alloc(ctx, buckets_for(tot_c), &new_cs);
-	if (rc == SYZSIG_OK)
-		rc = ms ? set_reserve(ms, tot_m) : set_alloc(ctx, buckets_for(tot_m), &new_ms);
-	if (rc == SYZSIG_OK)
-		rc = counters_reset(ctx);
-	if (rc == SYZSIG_OK) {
-		const hipError_t e = hipMemsetAsync(M.flag, 0, nseg, s);
-		rc = e == hipSuccess ? SYZSIG_OK : hip_fail(e, "hipMemsetAsync", __FILE__, __LINE__);
-	}
-	if (rc != SYZSIG_OK) {
-		syzsig_set_free(new_cs);
-		syzsig_set_free(new_ms);
-		return rc;
-	}
-	cs = cs ? cs : new_cs;  // (still NULL when no INPUT segment has an entry: no kernel then touches it)
-	ms = ms ? ms : new_ms;
+	Receiver cs, ms;
+	if (tot_c)  // (not opened when no INPUT segment has an entry: no kernel then touches corpusSignal)
+		SYZ_TRY(cs.open(ctx, corpus_signal, tot_c));
+	SYZ_TRY(ms.open(ctx, max_signal, tot_m));
+	SYZ_TRY(counters_reset(ctx));
+	SYZ_HIP(hipMemsetAsync(M.flag, 0, nseg, s));
 	if (n_short)
 		k_pr_short<<<grid_cap(nseg, 1u << 16), kPrThreads, 0, s>>>(d_seg_off, d_seg_kind, nseg, d_elems, d_prios,
-		                                                           cs ? cs->slots : nullptr, cs ? cs->nbuckets - 1 : 0,
-		                                                           ms->slots, ms->nbuckets - 1, M.flag, ctx->d_cnt);
+		                                                           cs.slots(), cs.bmask(), ms.slots(), ms.bmask(), M.flag,
+		                                                           ctx->d_cnt);
 	if (n_long)
-		rc = pr_long(ctx, A, M, nchunks, nbuckets, (uint64_t*)tab, cs, ms);
-	if (rc == SYZSIG_OK) {
-		const hipError_t e = hipGetLastError();
-		rc = e == hipSuccess ? counters_fetch(ctx) : hip_fail(e, "k_pr_short", __FILE__, __LINE__);
-	}
-	if (rc == SYZSIG_OK && ctx->h_cnt[kCntOverflow])
-		rc = fail(SYZSIG_EIO, "fuzzer_poll_res: internal: a reserved table overflowed");
-	if (rc != SYZSIG_OK) {
-		syzsig_set_free(new_cs);
-		syzsig_set_free(new_ms);
-		return rc;
-	}
-	if (cs)
-		cs->len += ctx->h_cnt[kPrInsC];
-	ms->len += ctx->h_cnt[kPrInsM];
-	*corpus_signal = cs;
-	*max_signal = ms;
+		SYZ_TRY(pr_long(ctx, A, M, nchunks, nbuckets, (uint64_t*)tab, cs, ms));
+	SYZ_TRY(commit_tail(ctx, "fuzzer_poll_res"));
+	cs.commit(ctx->h_cnt[kPrInsC]);
+	ms.commit(ctx->h_cnt[kPrInsM]);
 	const uint64_t n_flagged = ctx->h_cnt[kPrLdsFail];
 	uint64_t losers = ctx->h_cnt[kPrLosers], tab_bytes = n_long ? nbuckets * kBucketSlots * sizeof(uint64_t) : 0;
 	if (n_flagged) {  // the segments whose LDS table had no room: the long path, in a second round
@@ -453,12 +406,9 @@ extern "C" int syzsig_fuzzer_poll_res_dev(syzsig_ctx* ctx, const uint64_t* d_seg
 		SYZ_TRY(ws_get(ctx, kWsPrTable, nbuckets * kBucketSlots * sizeof(uint64_t), &tab));
 		SYZ_TRY(counters_reset(ctx));
 		SYZ_TRY(pr_long(ctx, A, M, nchunks, nbuckets, (uint64_t*)tab, cs, ms));
-		SYZ_TRY(counters_fetch(ctx));
-		if (cs)
-			cs->len += ctx->h_cnt[kPrInsC];
-		ms->len += ctx->h_cnt[kPrInsM];
-		if (ctx->h_cnt[kCntOverflow])
-			return fail(SYZSIG_EIO, "fuzzer_poll_res: internal: a reserved table overflowed");
+		SYZ_TRY(commit_tail(ctx, "fuzzer_poll_res"));
+		cs.commit(ctx->h_cnt[kPrInsC]);  // (the sets are the caller's since the first round: the lengths only)
+		ms.commit(ctx->h_cnt[kPrInsM]);
 		losers += ctx->h_cnt[kPrLosers];
 		tab_bytes = std::max<uint64_t>(tab_bytes, nbuckets * kBucketSlots * sizeof(uint64_t));
 	}
@@ -472,9 +422,5 @@ extern "C" int syzsig_fuzzer_poll_res_dev(syzsig_ctx* ctx, const uint64_t* d_seg
 
 extern "C" int syzsig_poll_res_stats(syzsig_ctx* ctx, uint64_t out[4])
 {
-	SYZ_LOCK(ctx);
-	if (!ctx || !out)
-		return fail(SYZSIG_EINVAL, "poll_res_stats: NULL argument");
-	std::copy(ctx->pr_stats, ctx->pr_stats + 4, out);
-	return SYZSIG_OK;
+	return stats_copy(ctx, &syzsig_ctx::pr_stats, out, "poll_res_stats");
 }

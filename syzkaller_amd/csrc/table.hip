@@ -412,10 +412,7 @@ int set_rehash(syzsig_set* s, uint64_t nbuckets, bool drop_absent)
 	SYZ_TRY(counters_reset(ctx));
 	k_rehash<<<grid_for(s->nslots(), 256), 256, 0, ctx->stream>>>(s->slots, s->nslots(), n->slots,
 	                                                               nbuckets - 1, drop_absent, ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
-	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->h_cnt[kCntOverflow])
-		return fail(SYZSIG_EIO, "rehash overflow (internal error)");
+	SYZ_TRY(commit_tail(ctx, "rehash"));
 	bool had_triage = s->firsts != nullptr;
 	set_release_storage(s);
 	s->slots = n->slots;
@@ -460,10 +457,7 @@ int merge_pairs_dev(syzsig_ctx* ctx, syzsig_set* dst, const uint64_t* d_pairs, u
 	SYZ_TRY(set_reserve(dst, n));
 	SYZ_TRY(counters_reset(ctx));
 	k_merge_pairs<<<grid_for(n, 256), 256, 0, ctx->stream>>>(dst->slots, dst->nbuckets - 1, d_pairs, n, ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
-	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->h_cnt[kCntOverflow])
-		return fail(SYZSIG_EIO, "merge overflow (internal error)");
+	SYZ_TRY(commit_tail(ctx, "merge_pairs"));
 	dst->len += ctx->h_cnt[kCntInserted];
 	return SYZSIG_OK;
 }
@@ -476,23 +470,15 @@ static int make_result(syzsig_ctx* ctx, uint64_t bound, bool nil_if_empty, syzsi
 	*out = nullptr;
 	syzsig_set* r = nullptr;
 	SYZ_TRY(set_alloc(ctx, buckets_for(bound), &r));
-	int rc = counters_reset(ctx);
-	if (rc == SYZSIG_OK) {
-		launch(r);
-		hipError_t e = hipGetLastError();
-		rc = e == hipSuccess ? counters_fetch(ctx) : hip_fail(e, "kernel launch", __FILE__, __LINE__);
-	}
-	if (rc == SYZSIG_OK && ctx->h_cnt[kCntOverflow])
-		rc = fail(SYZSIG_EIO, "result table overflow (internal error)");
-	if (rc != SYZSIG_OK) {
-		syzsig_set_free(r);
-		return rc;
-	}
+	OwnedSets own;
+	own.add(r);
+	SYZ_TRY(counters_reset(ctx));
+	launch(r);
+	SYZ_TRY(commit_tail(ctx, "result"));
 	r->len = ctx->h_cnt[kCntInserted];
-	if (nil_if_empty && r->len == 0) {
-		syzsig_set_free(r);
+	if (nil_if_empty && r->len == 0)
 		return SYZSIG_OK;
-	}
+	own.release();
 	*out = r;
 	return SYZSIG_OK;
 }
@@ -889,19 +875,16 @@ int syzsig_intersection(syzsig_ctx* ctx, const syzsig_set* s, const syzsig_set* 
 // carry prio 0 (map[uint32]struct{}: the value is unused).
 static int cover_merge_dev(syzsig_ctx* ctx, syzsig_set** cov, const uint32_t* d_raw, uint64_t n)
 {
-	if (!*cov)
-		SYZ_TRY(syzsig_set_make(ctx, n, cov));
-	if (n == 0)
-		return SYZSIG_OK;
-	syzsig_set* s = *cov;
-	SYZ_TRY(set_reserve(s, n));
-	SYZ_TRY(counters_reset(ctx));
-	k_from_raw<<<grid_for(n, 256), 256, 0, ctx->stream>>>(s->slots, s->nbuckets - 1, d_raw, n, 0, ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
-	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->h_cnt[kCntOverflow])
-		return fail(SYZSIG_EIO, "cover merge overflow (internal error)");
-	s->len += ctx->h_cnt[kCntInserted];
+	Receiver r;
+	SYZ_TRY(r.open(ctx, cov, n));
+	uint64_t inserted = 0;
+	if (n) {
+		SYZ_TRY(counters_reset(ctx));
+		k_from_raw<<<grid_for(n, 256), 256, 0, ctx->stream>>>(r.slots(), r.bmask(), d_raw, n, 0, ctx->d_cnt);
+		SYZ_TRY(commit_tail(ctx, "cover_merge"));
+		inserted = ctx->h_cnt[kCntInserted];
+	}
+	r.commit(inserted);
 	return SYZSIG_OK;
 }
 
@@ -932,18 +915,13 @@ int syzsig_merge(syzsig_ctx* ctx, syzsig_set** sp, const syzsig_set* s1)
 	SYZ_TRY(set_check_idle(s1));
 	if (syzsig_empty(s1))
 		return SYZSIG_OK;  // signal.go:118-120
-	if (!*sp)
-		SYZ_TRY(syzsig_set_make(ctx, s1->len, sp));  // signal.go:121-125
-	syzsig_set* s = *sp;
-	SYZ_TRY(set_reserve(s, s1->len));
+	Receiver r;
+	SYZ_TRY(r.open(ctx, sp, s1->len));  // signal.go:121-125: a nil receiver is allocated
 	SYZ_TRY(counters_reset(ctx));
-	k_merge<<<grid_for(s1->nslots(), 256), 256, 0, ctx->stream>>>(s->slots, s->nbuckets - 1, s1->slots, s1->nslots(),
+	k_merge<<<grid_for(s1->nslots(), 256), 256, 0, ctx->stream>>>(r.slots(), r.bmask(), s1->slots, s1->nslots(),
 	                                                               ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
-	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->h_cnt[kCntOverflow])
-		return fail(SYZSIG_EIO, "merge overflow (internal error)");
-	s->len += ctx->h_cnt[kCntInserted];
+	SYZ_TRY(commit_tail(ctx, "merge"));
+	r.commit(ctx->h_cnt[kCntInserted]);
 	return SYZSIG_OK;
 }
 

@@ -47,6 +47,7 @@ INTERSECTION = [
 MERGE = [
     ("118-120 nil.Merge(nil) stays nil", None, None, None),
     ("118-120 merge of empty is a no-op", {1: 1}, {}, {1: 1}),
+    ("118-120 nil.Merge(non-nil empty) stays nil", None, {}, None),
     ("121-125 nil receiver is allocated", None, {1: 1}, {1: 1}),
     ("127 max prio", {1: 1, 2: 3}, {1: 2, 2: 1, 3: -1}, {1: 2, 2: 3, 3: -1}),
 ]

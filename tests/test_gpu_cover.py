@@ -19,6 +19,16 @@ def test_cover_nil_and_empty(gpu):
     assert not c.is_nil() and o.c is not None and len(c) == 0
 
 
+def test_cover_empty_merge_into_existing(gpu):
+    from syzkaller_amd.signal import Cover
+
+    c, o = Cover(gpu.eng), O.OCover()
+    for raw in ([5, 6], [], [6, 7], []):
+        c.Merge(np.array(raw, np.uint32))
+        o.Merge(raw)
+        assert len(c) == len(o.c) and sorted(c.Serialize().tolist()) == sorted(o.Serialize())
+
+
 def test_cover_merge_matches_restatement(gpu):
     from syzkaller_amd.signal import Cover
 

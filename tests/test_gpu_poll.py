@@ -126,6 +126,30 @@ def test_poll_batch_empty_and_nil_max(gpu):
     assert nm[0].is_nil() and nm[1].is_nil() and nm[2].to_dict() == {7: 0, 8: 2}
 
 
+def test_poll_batch_nil_max_stays_nil_without_events(gpu):
+    """manager.go:1033-1034: maxSignal.Merge runs only for a non-empty newMax, so
+    a nil maxSignal polled with empty Serials stays nil -- while a newMaxSignal
+    from before the batch still goes out as its fuzzer's reply."""
+    from syzkaller_amd import signal as S
+
+    pre = (np.array([3, 4], np.uint32), np.array([1, 0], np.int8))
+    empty = (np.empty(0, np.uint32), np.empty(0, np.int8))
+    order = [1, 0, 0]
+    ms, nm = S.Signal(None, gpu.eng), [S.Serial(*pre).Deserialize(gpu.eng), S.Signal(None, gpu.eng)]
+    rep = S.manager_poll(ms, nm, [(f, S.Serial()) for f in order], gpu.eng)
+    oms, onm = O.OSig(), [O.deserialize(*pre), O.OSig()]
+    for i, f in enumerate(order):
+        re, rp = O.poll(oms, onm, f, empty)
+        assert dict(zip(rep[i].Elems.tolist(), rep[i].Prios.tolist())) == dict(zip(re.tolist(), rp.tolist())), f"reply {i}"
+    assert dict(zip(rep[1].Elems.tolist(), rep[1].Prios.tolist())) == {3: 1, 4: 0}
+    assert ms.is_nil() and oms.is_nil() and nm[0].is_nil() and nm[1].is_nil()
+    # an existing maxSignal polled at or below its prios: no event either, nothing changes
+    ms = S.Serial(*pre).Deserialize(gpu.eng)
+    rep = S.manager_poll(ms, nm, [(0, S.Serial([3, 4, 3], [1, -1, 0]))], gpu.eng)
+    assert rep[0].Elems.size == 0 and ms.to_dict() == {3: 1, 4: 0} and ms.Len() == 2
+    assert nm[0].is_nil() and nm[1].is_nil()
+
+
 @pytest.mark.parametrize("case", ["forced_sequential", "hot_element"])
 def test_poll_batch_sequential_path_vs_oracle(gpu, case):
     """The batch's exact fallback (csrc/poll.hip poll_sequential: the
