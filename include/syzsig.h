@@ -63,7 +63,8 @@ int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
  * kernels of the last syzsig_edge_derive_dev / syzsig_minimize_dev call, or the
  * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev,
  * syzsig_triage_cover_dev, syzsig_triage_items_dev, syzsig_exec_comps_dev,
- * syzsig_comp_map_dev or syzsig_shrink_expand_dev call (uploads / first kernel to its last kernel,
+ * syzsig_comp_map_dev, syzsig_shrink_expand_dev or syzsig_hint_mutants_dev call (uploads / first kernel to its
+ * last kernel,
  * including the host round trips between); for syzsig_manager_new_input_batch
  * the host wall time of the call, which ends synchronised. */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
@@ -662,6 +663,51 @@ int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_off, const u
                              uint64_t npairs, const uint32_t* d_q_call, const uint64_t* d_q_val, uint64_t nq,
                              const uint64_t* special_ints, uint32_t nspecial, uint64_t* d_rep_off, uint64_t* d_rep,
                              uint64_t cap, uint64_t* n_out);
+
+/* SYZSIG_HINT_LIST: the capacity of the per-arg list of (window, replacer)
+ * candidates that one workgroup of syzsig_hint_mutants_dev sorts in LDS (16 B
+ * each).  An arg with more accepted candidates than this, or with one lookup
+ * whose key has more values than this, takes the exact fallback through the
+ * internals of syzsig_shrink_expand_dev; the results do not depend on the path.
+ * SYZSIG_HINT_MAX_DATA: maxDataLength, prog/hints.go:38. */
+#define SYZSIG_HINT_LIST 1024
+#define SYZSIG_HINT_MAX_DATA 100
+
+/* prog/hints.go:105-132, the inner half of generateHints (:82-103) for narg
+ * args of a batch against the maps of syzsig_comp_map_dev (npairs =
+ * map_off[ncalls]); the caller has applied the type filter of :83-95.  Arg a
+ * is matched against the map of call arg_call[a].
+ *  - arg_kind[a] = 0, a ConstArg (checkConstArg, :105-112): one window, v =
+ *    arg_val[a]; every replacer of shrinkExpand(v, map) (:164-218) is a mutant
+ *    (at = 0, nb = 8, rep).  Its range in arg_off must be empty.
+ *  - arg_kind[a] = 1, a DataArg (checkDataArg, :114-132) whose L bytes are
+ *    d_data[arg_off[a] .. arg_off[a + 1]) (no alignment asked): windows i = 0 ..
+ *    min(L, 100) - 1, v = the little-endian u64 of data[i : i + 8], zero-padded
+ *    past L (:122-124); every replacer is a mutant (at = i, nb = min(8, L - i),
+ *    rep): the mutated arg is the original with bytes at .. at + nb set to the
+ *    low nb bytes of rep, little-endian (:126-127; copy() stops at the arg's
+ *    end).  rep is reported in full.
+ * Replacers are a set per window (uint64Set), a replacer equal to v included;
+ * the order is args as given, windows ascending, replacers ascending as
+ * unsigned (the fixed instance of Go's map order that shrink_expand uses).  Arg
+ * a's mutants are entries mut_off[a] .. mut_off[a + 1] of d_mut_at, d_mut_nb
+ * and d_mut_rep (cap entries each); mut_off has narg + 1 entries; *n_out = the
+ * total.  If it exceeds cap nothing of the caller's is written: SYZSIG_ERANGE
+ * with the needed total in *n_out.  special_ints as for
+ * syzsig_shrink_expand_dev.  SYZSIG_EINVAL (nothing written): a NULL argument,
+ * an arg_call outside the maps, a kind other than 0 / 1, an arg_off that
+ * decreases or passes nbytes, a ConstArg with a non-empty range, more than
+ * 2^25 args.  narg = 0 writes mut_off[0] = 0. */
+int syzsig_hint_mutants_dev(syzsig_ctx* ctx, const uint64_t* d_map_off, const uint64_t* d_pairs, uint64_t ncalls,
+                            uint64_t npairs, const uint32_t* d_arg_call, const uint8_t* d_arg_kind,
+                            const uint64_t* d_arg_val, const uint64_t* d_arg_off, const uint8_t* d_data,
+                            uint64_t narg, uint64_t nbytes, const uint64_t* special_ints, uint32_t nspecial,
+                            uint64_t* d_mut_off, uint32_t* d_mut_at, uint8_t* d_mut_nb, uint64_t* d_mut_rep,
+                            uint64_t cap, uint64_t* n_out);
+/* The paths of the last syzsig_hint_mutants_dev call: out[0] = args resolved
+ * in LDS, out[1] = args that took the fallback, out[2] = windows examined,
+ * out[3] = accepted candidates before the per-window dedup. */
+int syzsig_hint_mutants_stats(syzsig_ctx* ctx, uint64_t out[4]);
 
 /* ---- hash-sharded maxSignal across GPUs (one process per GPU) ----
  * The batch is split by program range over G GPUs (serial order = GPU-major);

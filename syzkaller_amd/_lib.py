@@ -34,6 +34,8 @@ SYZSIG_POLLRES_TILE = 4096  # a poll reply's Serial past it leaves the one-workg
 SYZSIG_SEG_MAXSIGNAL = 0  # syzsig_fuzzer_poll_res_dev: a reply's MaxSignal (fuzzer.go:344-347)
 SYZSIG_SEG_INPUT = 1  # ... the Signal of one of its NewInputs (fuzzer.go:348-350)
 SYZSIG_INPUT_PRESENT = 1  # a NewInput batch row that is the key's old corpus entry
+SYZSIG_HINT_LIST = 1024  # the per-arg candidate list of syzsig_hint_mutants_dev in LDS (hints.hip)
+SYZSIG_HINT_MAX_DATA = 100  # prog/hints.go:38 maxDataLength
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
 SYZSIG_INGEST_ECOMPTYPE = 9
@@ -158,6 +160,9 @@ SIGNATURES = {
     "syzsig_comp_map_dev": (c_int, [_P, _P, c_uint64, _P, _P, _P, c_uint64, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     "syzsig_shrink_expand_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, _P, c_uint64, _P, c_uint32, _P, _P,
                                          c_uint64, POINTER(c_uint64)]),
+    "syzsig_hint_mutants_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, _P, _P, _P, _P, c_uint64, c_uint64, _P,
+                                        c_uint32, _P, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
+    "syzsig_hint_mutants_stats": (c_int, [_P, _P]),
     "syzsig_ingest_exec_output_dev": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P, _P, _P, _P,
                                               _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_triage_records_dev": (c_int, [_P, _P, _PP, _P, c_uint64, _P, c_uint32, _P,

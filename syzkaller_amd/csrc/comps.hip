@@ -9,7 +9,9 @@
 //       (syzsig_exec_comps_dev);
 //   pkg/ipc/ipc.go:420-465        the records parsed back into prog.CompMap
 //       through CompMap.AddComp (prog/hints.go:43-48) (syzsig_comp_map_dev);
-//   prog/hints.go:164-218         shrinkExpand (syzsig_shrink_expand_dev).
+//   prog/hints.go:164-218         shrinkExpand (syzsig_shrink_expand_dev; its
+//       per-candidate rule is shrinkexpand.h's, and se_queries, its body over
+//       device-resident queries, is also the fallback of hints.hip).
 // All three reduce to one operation per segment -- sort ascending, drop equal
 // neighbours, write the survivors -- over keys of 3, 2 and 1 u64 words: the
 // comparison triple; the (key, value) pair of the map; a replacer.
@@ -23,7 +25,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "segsort.h"
+#include "shrinkexpand.h"
 
 namespace syz {
 
@@ -33,9 +35,6 @@ namespace syz {
 constexpr uint32_t kCmTile = SYZ_COMPS_TILE;
 constexpr uint32_t kCmThreads = kSuThreads;
 constexpr uint32_t kCmMaxComps = 65535;       // executor.h:581-582: 8 + 32 n bytes fit kCoverSize * 8
-constexpr uint32_t kCmMaxSeg = 0x7fffffffu;   // keys per segment
-constexpr uint32_t kCmVariants = 12;          // hints.go:165-191: 7 widths little-endian, 5 big-endian (not at width 1)
-constexpr uint32_t kCmMaxSpecial = 4096;
 constexpr uint64_t kCmMaxOutput = 16ull << 20;  // executor.h kMaxOutput
 constexpr uint32_t kCmpConst = 1, kCmpSizeMask = 6, kCmpSize1 = 0, kCmpSize2 = 2, kCmpSize8 = 6;  // executor.h:147-152
 static_assert((kCmTile & (kCmTile - 1)) == 0 && kCmTile >= kCmThreads, "tile: a power of two, at least one sweep");
@@ -247,35 +246,7 @@ __global__ __launch_bounds__(64) void k_cm_walk(const uint32_t* __restrict__ wor
 
 // ---- syzsig_shrink_expand_dev ----
 
-__device__ __forceinline__ uint64_t cm_swap(uint64_t v, uint32_t width)  // prog/mutation.go:566-579
-{
-	if (width == 2)
-		return __builtin_bswap16((uint16_t)v);
-	if (width == 4)
-		return __builtin_bswap32((uint32_t)v);
-	if (width == 8)
-		return __builtin_bswap64(v);
-	return v;
-}
-
-// variant x of hints.go:165-191: widths 8, 4, 2, 1, -4, -2, -1 little-endian
-// (x = 0..6), then 8, 4, 2, -4, -2 big-endian (x = 7..11)
-__device__ __forceinline__ void cm_variant(uint32_t x, uint32_t& width, bool& expand, bool& be)
-{
-	const uint32_t le_w[7] = {8, 4, 2, 1, 4, 2, 1}, be_w[5] = {8, 4, 2, 4, 2};
-	be = x >= 7;
-	width = be ? be_w[x - 7] : le_w[x];
-	expand = be ? x >= 10 : x >= 4;
-}
-
-__device__ __forceinline__ uint64_t cm_mask(uint32_t width) { return width == 8 ? ~0ull : (1ull << (8 * width)) - 1; }
-
-__device__ __forceinline__ uint64_t cm_mutant(uint64_t v, uint32_t width, bool expand, bool be)
-{
-	const uint64_t mask = cm_mask(width);
-	const uint64_t m = expand ? v | ~mask : v & mask;  // hints.go:168-176
-	return be ? cm_swap(m, width) : m;                 // hints.go:186-191
-}
+// (the per-candidate rule -- cm_variant, cm_mutant, cm_values, cm_replacer -- is shrinkexpand.h's)
 
 // per (query, variant): the range of the call's pairs whose key is the mutant
 __global__ __launch_bounds__(256) void k_se_count(const uint64_t* __restrict__ map_off,
@@ -304,21 +275,12 @@ __global__ __launch_bounds__(256) void k_se_count(const uint64_t* __restrict__ m
 			uint32_t width;
 			bool expand, be;
 			cm_variant(x, width, expand, be);
-			const uint64_t m = cm_mutant(q_val[q], width, expand, be);
-			// the first pair with key >= m, then from there the first with key > m
-			const uint64_t first = su_search(a, b, [&](uint64_t i) { return pairs[2 * i] < m; });
-			const uint64_t past = su_search(first, b, [&](uint64_t i) { return pairs[2 * i] <= m; });
+			uint64_t first;
+			vcnt[g] = cm_values(pairs, a, b, cm_mutant(q_val[q], width, expand, be), first);
 			vlo[g] = first;
-			vcnt[g] = (uint32_t)(past - first);
 		}
 	}
 	block_count(&cnt[kCntError], err);
-}
-
-__device__ __forceinline__ bool cm_is_special(const uint64_t* __restrict__ sp, uint32_t nsp, uint64_t v)
-{
-	const uint32_t lo = su_search(0u, nsp, [&](uint32_t i) { return sp[i] < v; });
-	return lo < nsp && sp[lo] == v;
 }
 
 // hints.go:192-213, one wave per query: the accepted replacers of variant x
@@ -343,22 +305,11 @@ __global__ __launch_bounds__(256) void k_se_write(const uint64_t* __restrict__ p
 		uint32_t width;
 		bool expand, be;
 		cm_variant(x, width, expand, be);
-		const uint64_t mask = cm_mask(width);
 		uint32_t run = 0;
 		for (uint32_t base = 0; base < n; base += 64) {
 			const uint32_t i = base + lane;
-			bool acc = false;
 			uint64_t rep = 0;
-			if (i < n) {
-				uint64_t nv = pairs[2 * (lo + i) + 1];
-				const uint64_t hi = nv & ~mask;
-				nv &= mask;
-				acc = hi == 0 || (hi ^ ~mask) == 0;  // hints.go:194-198
-				if (be)
-					nv = cm_swap(nv, width);  // hints.go:199-201
-				acc = acc && !cm_is_special(special, nspecial, nv);  // hints.go:202-204
-				rep = (v & ~mask) | nv;  // hints.go:207
-			}
+			const bool acc = i < n && cm_replacer(v, pairs[2 * (lo + i) + 1], width, be, special, nspecial, rep);
 			const uint64_t m = __ballot(acc);
 			if (acc)
 				o[run + lane_rank(m)] = rep;
@@ -395,6 +346,61 @@ static int cm_emit_csr(syzsig_ctx* ctx, const char* what, const uint64_t* stage,
 		SYZ_HIP(hipMemcpyAsync(d_status, status, nseg * 4, hipMemcpyDeviceToDevice, s));
 	SYZ_TRY(su_time_end(ctx));
 	SYZ_HIP(hipStreamSynchronize(s));
+	return SYZSIG_OK;
+}
+
+// shrinkexpand.h: the body of syzsig_shrink_expand_dev over device-resident queries
+int se_queries(syzsig_ctx* ctx, const char* what, const uint64_t* d_map_off, const uint64_t* d_pairs, uint64_t ncalls,
+               uint64_t npairs, const uint32_t* d_q_call, const uint64_t* d_q_val, uint64_t nq,
+               const uint64_t* special_ints, uint32_t nspecial, bool timed, SeOut* out)
+{
+	const hipStream_t s = ctx->stream;
+	const std::string who = what;
+	const uint64_t nv = nq * kCmVariants;
+	// vlo[nv], voff[nv + 1], vcnt[nv], src_len[nv], seg_len[nq], cnt[nq], off[nq + 1], special[nspecial]
+	char* d;
+	const size_t o_voff = align256(nv * 8), o_vcnt = o_voff + align256((nv + 1) * 8), o_sl = o_vcnt + align256(nv * 4),
+	             o_seg = o_sl + align256(nv * 4), o_cnt = o_seg + align256(nq * 4), o_off = o_cnt + align256(nq * 4),
+	             o_sp = o_off + align256((nq + 1) * 8);
+	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_sp + align256((size_t)nspecial * 8 + 8), (void**)&d));
+	uint64_t *vlo = (uint64_t*)d, *voff = (uint64_t*)(d + o_voff), *off = (uint64_t*)(d + o_off),
+	         *special = (uint64_t*)(d + o_sp);
+	uint32_t *vcnt = (uint32_t*)(d + o_vcnt), *src_len = (uint32_t*)(d + o_sl), *seg_len = (uint32_t*)(d + o_seg),
+	         *cnt = (uint32_t*)(d + o_cnt);
+	std::vector<uint64_t> sp(special_ints, special_ints + nspecial);
+	std::sort(sp.begin(), sp.end());
+	SYZ_TRY(counters_reset(ctx));
+	if (nspecial) {  // (pageable: the copy has left sp when the call returns)
+		SYZ_HIP(hipMemcpyAsync(special, sp.data(), (size_t)nspecial * 8, hipMemcpyHostToDevice, s));
+		SYZ_HIP(hipStreamSynchronize(s));
+	}
+	if (timed)
+		SYZ_TRY(su_time_begin(ctx));
+	k_se_count<<<(int)((nv + 255) / 256), 256, 0, s>>>(d_map_off, d_pairs, ncalls, npairs, d_q_call, d_q_val, nq, vlo,
+	                                                   vcnt, ctx->d_cnt);
+	k_su_scan<<<1, kCmThreads, 0, s>>>(vcnt, nv, voff);
+	SYZ_HIP(hipGetLastError());
+	uint64_t ncand = 0;
+	SYZ_HIP(hipMemcpyAsync(&ncand, voff + nv, 8, hipMemcpyDeviceToHost, s));
+	SYZ_TRY(counters_fetch(ctx));
+	if (ctx->h_cnt[kCntError])
+		return fail(SYZSIG_EINVAL, who + ": a query's call is outside the map, or the map's offsets are not "
+		                                 "ascending inside its pairs");
+	void *cand, *stage2;
+	SYZ_TRY(ws_get(ctx, kWsSuStage, ncand * 8 + 256, &cand));
+	SYZ_TRY(ws_get(ctx, kWsSuStage2, ncand * 8 + 256, &stage2));
+	k_se_write<<<(int)((nq + 3) / 4), 256, 0, s>>>(d_pairs, d_q_val, nq, vlo, vcnt, voff, special, nspecial,
+	                                               (uint64_t*)cand, src_len);
+	k_cm_prep_sources<<<(int)((nq + 255) / 256), 256, 0, s>>>(src_len, kCmVariants, nq, seg_len, ctx->d_cnt);
+	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(counters_fetch(ctx));
+	if (ctx->h_cnt[kCntOverflow])
+		return fail(SYZSIG_ERANGE, who + ": a query has 2^31 or more candidates");
+	const SuSegs S{cand, 1, voff, src_len, kCmVariants, seg_len, nq};
+	// a query's survivors go to the head of its own candidate range in stage2
+	const SuOutKeys<SuU64<1>> pol{(uint64_t*)stage2, voff, kCmVariants, cnt};
+	SYZ_TRY((su_sort_unique<CmTile<1>, SuOutKeys<SuU64<1>>>(ctx, S, pol)));
+	*out = SeOut{(const uint64_t*)stage2, voff, cnt, seg_len, off};
 	return SYZSIG_OK;
 }
 
@@ -515,49 +521,9 @@ extern "C" int syzsig_shrink_expand_dev(syzsig_ctx* ctx, const uint64_t* d_map_o
 		SYZ_HIP(hipStreamSynchronize(s));
 		return SYZSIG_OK;
 	}
-	const uint64_t nv = nq * kCmVariants;
-	// vlo[nv], voff[nv + 1], vcnt[nv], src_len[nv], seg_len[nq], cnt[nq], off[nq + 1], special[nspecial]
-	char* d;
-	const size_t o_voff = align256(nv * 8), o_vcnt = o_voff + align256((nv + 1) * 8), o_sl = o_vcnt + align256(nv * 4),
-	             o_seg = o_sl + align256(nv * 4), o_cnt = o_seg + align256(nq * 4), o_off = o_cnt + align256(nq * 4),
-	             o_sp = o_off + align256((nq + 1) * 8);
-	SYZ_TRY(ws_get(ctx, kWsSuMeta, o_sp + align256((size_t)nspecial * 8 + 8), (void**)&d));
-	uint64_t *vlo = (uint64_t*)d, *voff = (uint64_t*)(d + o_voff), *off = (uint64_t*)(d + o_off),
-	         *special = (uint64_t*)(d + o_sp);
-	uint32_t *vcnt = (uint32_t*)(d + o_vcnt), *src_len = (uint32_t*)(d + o_sl), *seg_len = (uint32_t*)(d + o_seg),
-	         *cnt = (uint32_t*)(d + o_cnt);
-	std::vector<uint64_t> sp(special_ints, special_ints + nspecial);
-	std::sort(sp.begin(), sp.end());
-	SYZ_TRY(counters_reset(ctx));
-	if (nspecial) {  // (pageable: the copy has left sp when the call returns)
-		SYZ_HIP(hipMemcpyAsync(special, sp.data(), (size_t)nspecial * 8, hipMemcpyHostToDevice, s));
-		SYZ_HIP(hipStreamSynchronize(s));
-	}
-	SYZ_TRY(su_time_begin(ctx));
-	k_se_count<<<(int)((nv + 255) / 256), 256, 0, s>>>(d_map_off, d_pairs, ncalls, npairs, d_q_call, d_q_val, nq, vlo,
-	                                                   vcnt, ctx->d_cnt);
-	k_su_scan<<<1, kCmThreads, 0, s>>>(vcnt, nv, voff);
-	SYZ_HIP(hipGetLastError());
-	uint64_t ncand = 0;
-	SYZ_HIP(hipMemcpyAsync(&ncand, voff + nv, 8, hipMemcpyDeviceToHost, s));
-	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->h_cnt[kCntError])
-		return fail(SYZSIG_EINVAL, "shrink_expand: a query's call is outside the map, or the map's offsets are not "
-		                           "ascending inside its pairs");
-	void *cand, *stage2;
-	SYZ_TRY(ws_get(ctx, kWsSuStage, ncand * 8 + 256, &cand));
-	SYZ_TRY(ws_get(ctx, kWsSuStage2, ncand * 8 + 256, &stage2));
-	k_se_write<<<(int)((nq + 3) / 4), 256, 0, s>>>(d_pairs, d_q_val, nq, vlo, vcnt, voff, special, nspecial,
-	                                               (uint64_t*)cand, src_len);
-	k_cm_prep_sources<<<(int)((nq + 255) / 256), 256, 0, s>>>(src_len, kCmVariants, nq, seg_len, ctx->d_cnt);
-	SYZ_HIP(hipGetLastError());
-	SYZ_TRY(counters_fetch(ctx));
-	if (ctx->h_cnt[kCntOverflow])
-		return fail(SYZSIG_ERANGE, "shrink_expand: a query has 2^31 or more candidates");
-	const SuSegs S{cand, 1, voff, src_len, kCmVariants, seg_len, nq};
-	// a query's survivors go to the head of its own candidate range in stage2
-	const SuOutKeys<SuU64<1>> pol{(uint64_t*)stage2, voff, kCmVariants, cnt};
-	SYZ_TRY((su_sort_unique<CmTile<1>, SuOutKeys<SuU64<1>>>(ctx, S, pol)));
-	return cm_emit_csr<1>(ctx, "shrink_expand", (const uint64_t*)stage2, voff, kCmVariants, cnt, off, nq,
-	                      d_rep_off, d_rep, cap, n_out);
+	SeOut o;
+	SYZ_TRY(se_queries(ctx, "shrink_expand", d_map_off, d_pairs, ncalls, npairs, d_q_call, d_q_val, nq, special_ints,
+	                   nspecial, true, &o));
+	return cm_emit_csr<1>(ctx, "shrink_expand", o.stage, o.voff, kCmVariants, o.cnt, o.off, nq, d_rep_off, d_rep, cap,
+	                      n_out);
 }

@@ -187,7 +187,12 @@ enum WsSlot : int {
 	kWsStepRecs = 61,
 	kWsStepFlags = 62,
 	kWsStepCursor = 63,
-	kWsCount = 64,
+	// hints.hip: the args' counts and offsets, the fast path's staged mutants, the fallback's queries
+	// (its fallback runs comps.hip's sort-unique inside the call: slots of its own)
+	kWsHmMeta = 64,
+	kWsHmStage = 65,
+	kWsHmQuery = 66,
+	kWsCount = 67,
 };
 
 // the debug flags that change only the path taken, never a result
@@ -249,6 +254,7 @@ struct syzsig_ctx {
 	uint64_t ni_stats[4] = {0, 0, 0, 0};  // syzsig_new_input_stats: the last NewInput batch's paths (corpus.hip)
 	uint64_t it_stats[4] = {0, 0, 0, 0};  // syzsig_triage_items_stats: the last triage_items call's paths (items.hip)
 	uint64_t pr_stats[4] = {0, 0, 0, 0};  // syzsig_poll_res_stats: the last fuzzer_poll_res call's paths (pollres.hip)
+	uint64_t hm_stats[4] = {0, 0, 0, 0};  // syzsig_hint_mutants_stats: the last hint_mutants call's paths (hints.hip)
 };
 
 struct syzsig_set {

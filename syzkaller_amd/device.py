@@ -227,6 +227,55 @@ class Device:
             rep = torch.empty(0, dtype=torch.int64, device=self.dev)
         return off, rep[: n.value]
 
+    def hint_mutants(self, map_off, pairs, arg_call, arg_kind, arg_val, arg_off, data, special_ints=(), out=None):
+        """prog/hints.go:105-132 for a batch of args against the maps of
+        comp_map (syzsig_hint_mutants_dev).  arg_call int32[narg], arg_kind
+        uint8[narg] (0 = ConstArg, 1 = DataArg), arg_val int64[narg], arg_off
+        int64[narg + 1] into data uint8[nbytes].  Returns (mut_off
+        int64[narg + 1], at int32[total], nb uint8[total], rep int64[total]):
+        arg a's mutants at [mut_off[a], mut_off[a + 1]), windows ascending,
+        replacers ascending as unsigned.  out = (at, nb, rep) tensors to write
+        into; too small raises SyzsigError(SYZSIG_ERANGE) with .needed."""
+        at, nb, rep = out if out is not None else (None, None, None)
+        self._check_dev(map_off, pairs, arg_call, arg_kind, arg_val, arg_off, data, at, nb, rep)
+        narg = arg_call.numel()
+        if arg_kind.numel() != narg or arg_val.numel() != narg or arg_off.numel() != narg + 1:
+            raise ValueError("arg_call, arg_kind, arg_val need one entry per arg, arg_off one more")
+        if arg_kind.dtype != torch.uint8 or data.dtype != torch.uint8:
+            raise ValueError("arg_kind and data are uint8")
+        sp = [int(x) & 0xFFFFFFFFFFFFFFFF for x in special_ints]
+        csp = (ctypes.c_uint64 * max(len(sp), 1))(*sp)
+        off = torch.empty(narg + 1, dtype=torch.int64, device=self.dev)
+        n = ctypes.c_uint64()
+
+        def run(at, nb, rep):
+            cap = 0 if at is None else min(at.numel(), nb.numel(), rep.numel())
+            return self.L.syzsig_hint_mutants_dev(self.eng.h, _p(map_off), _p(pairs), map_off.numel() - 1,
+                                                  pairs.numel() // 2, _p(arg_call), _p(arg_kind), _p(arg_val),
+                                                  _p(arg_off), _p(data), narg, data.numel(), csp, len(sp), _p(off),
+                                                  _p(at), _p(nb), _p(rep), cap, ctypes.byref(n))
+        rc = run(at, nb, rep)
+        if out is None:
+            if rc == _lib.SYZSIG_ERANGE:
+                at = torch.empty(n.value, dtype=torch.int32, device=self.dev)
+                nb = torch.empty(n.value, dtype=torch.uint8, device=self.dev)
+                rep = torch.empty(n.value, dtype=torch.int64, device=self.dev)
+                rc = run(at, nb, rep)
+            elif rc == _lib.SYZSIG_OK:
+                at = torch.empty(0, dtype=torch.int32, device=self.dev)
+                nb = torch.empty(0, dtype=torch.uint8, device=self.dev)
+                rep = torch.empty(0, dtype=torch.int64, device=self.dev)
+        self._check_cap(rc, n)
+        return off, at[: n.value], nb[: n.value], rep[: n.value]
+
+    def hint_mutants_stats(self):
+        """(args resolved in LDS, args that took the fallback, windows
+        examined, accepted candidates before the dedup) of the last
+        hint_mutants call (syzsig_hint_mutants_stats)."""
+        out = (ctypes.c_uint64 * 4)()
+        check(self.L.syzsig_hint_mutants_stats(self.eng.h, out))
+        return tuple(int(x) for x in out)
+
     # ---------------------------------------------------------------- executor output ingest
     def ingest_exec_output(self, out, prog_off, prog_call, call_any, call_num=None, want_cover=False):
         """pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output
