@@ -63,8 +63,8 @@ int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
  * kernels of the last syzsig_edge_derive_dev / syzsig_minimize_dev call, or the
  * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev,
  * syzsig_triage_cover_dev, syzsig_triage_items_dev, syzsig_exec_comps_dev,
- * syzsig_comp_map_dev, syzsig_shrink_expand_dev or syzsig_hint_mutants_dev call (uploads / first kernel to its
- * last kernel,
+ * syzsig_comp_map_dev, syzsig_shrink_expand_dev, syzsig_hint_mutants_dev, syzsig_hash_dev or
+ * syzsig_sigset_add_dev call (uploads / first kernel to its last kernel,
  * including the host round trips between); for syzsig_manager_new_input_batch
  * the host wall time of the call, which ends synchronised. */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
@@ -219,8 +219,8 @@ int syzsig_manager_poll_batch(syzsig_ctx* ctx, syzsig_set** max_signal, syzsig_s
  * Row i (arrival order) is one RPC's a.RPCInput: its Serial a.Signal =
  * elems/prios[sig_off[i] .. sig_off[i+1]) (Deserialize rules: a later duplicate
  * overwrites), its a.Cover = cover[cover_off[i] .. cover_off[i+1]), and
- * input_key[i] < nkeys a dense index of hash.String(a.Prog) (sha1 stays with
- * the caller).  The result is the reference's loop over the rows under mgr.mu:
+ * input_key[i] < nkeys a dense index of hash.String(a.Prog) (syzsig_hash_dev
+ * and syzsig_number_sigs_dev give it for a batch).  The result is the reference's loop over the rows under mgr.mu:
  *   inputSignal := a.Signal.Deserialize()
  *   if corpusSignal.Diff(inputSignal).Empty() return          (:993: rejected)
  *   corpusSignal.Merge(inputSignal); corpusCover.Merge(a.Cover)   (:997-998)
@@ -708,6 +708,89 @@ int syzsig_hint_mutants_dev(syzsig_ctx* ctx, const uint64_t* d_map_off, const ui
  * in LDS, out[1] = args that took the fallback, out[2] = windows examined,
  * out[3] = accepted candidates before the per-window dedup. */
 int syzsig_hint_mutants_stats(syzsig_ctx* ctx, uint64_t out[4]);
+
+/* ---- pkg/hash/hash.go:14-26: type Sig [sha1.Size]byte, Hash, over a batch ----
+ * Message i is d_data[off[i] .. off[i + 1]) (d_off has nmsg + 1 entries), at any
+ * byte alignment; d_sig[20 i ..] receives its Sig: the SHA-1 digest bytes in
+ * order (each state word big-endian), what hash.Hash returns and Sig.String
+ * prints as hex.  Hash(pieces...) is the hash of the concatenation: the caller
+ * concatenates.  nmsg = 0 is SYZSIG_OK and writes nothing.
+ * SYZSIG_EINVAL, nothing written: a NULL d_off or d_sig with nmsg > 0, a NULL
+ * d_data with nbytes > 0, offsets that decrease, off[nmsg] > nbytes.
+ * SYZSIG_ERANGE, nothing written: a message longer than SYZSIG_HASH_MAX_MSG
+ * (its bit length then fits the low length word; the executor's input region
+ * is 2 MB), 2^32 or more messages.  The offsets are checked on device before
+ * any byte of d_data is read.
+ * Reads: no byte outside the messages' ranges is ever loaded, aligned or not.
+ * The 16-byte and 4-byte loads are of aligned chunks that lie wholly inside the
+ * span of one wave's messages (resp. inside one message); the bytes before the
+ * first and after the last such chunk are loaded one by one.  Nothing is assumed
+ * about the allocation's alignment or about room past d_data + nbytes.
+ * SYZSIG_HASH_STAGE: 64 consecutive messages are one wave's; when their bytes
+ * together are at most this many, the wave loads them coalesced into LDS and
+ * hashes from there, else each lane reads its own message from global memory.
+ * SYZSIG_HASH_LONG: a message longer than this is left to a second launch
+ * that takes only such messages, one per lane, so that it does not hold up the
+ * 63 others of its wave. */
+#define SYZSIG_SIG_BYTES 20
+#define SYZSIG_HASH_MAX_MSG (1ull << 28)
+#define SYZSIG_HASH_STAGE 32768
+#define SYZSIG_HASH_LONG 4096
+int syzsig_hash_dev(syzsig_ctx* ctx, const uint8_t* d_data, const uint64_t* d_off, uint64_t nmsg, uint64_t nbytes,
+                    uint8_t* d_sig);
+/* The paths of the last syzsig_hash_dev call: out[0] = messages hashed from LDS
+ * staging, out[1] = messages of the first launch read directly from global
+ * memory, out[2] = messages on the long list, out[3] = 64-byte blocks
+ * compressed. */
+int syzsig_hash_stats(syzsig_ctx* ctx, uint64_t out[4]);
+
+/* ---- sets keyed by hash.Sig: fuzzer.corpusHashes (syz-fuzzer/fuzzer.go:
+ * 447-452), mgr.hubCorpus (syz-manager/manager.go:1110-1113, :1142-1158), the
+ * keys of mgr.corpus ----
+ * A syzsig_sigset is a device-resident map[hash.Sig]struct{}: its Sigs sorted
+ * ascending as memcmp orders them.  NULL is the nil map: Len 0, usable wherever
+ * a set is read, and allocated by the entry points that write one.  Every d_sig
+ * is n Sigs of SYZSIG_SIG_BYTES bytes back to back in device memory, at any
+ * alignment.  One call takes at most 2^25 Sigs and a set holds at most 2^32 - 2
+ * (SYZSIG_ERANGE).  SYZSIG_SIGSET_TILE: the keys of one sort tile in LDS; a
+ * longer batch is tile-sorted and rank-merged through workspace buffers. */
+#define SYZSIG_SIGSET_TILE 2048
+typedef struct syzsig_sigset syzsig_sigset;
+int syzsig_sigset_make(syzsig_ctx* ctx, syzsig_sigset** out);
+void syzsig_sigset_free(syzsig_sigset* s);
+uint64_t syzsig_sigset_len(const syzsig_sigset* s);
+/* addInputToCorpus's `if _, ok := fuzzer.corpusHashes[sig]; !ok` (fuzzer.go:
+ * 447-452) over a batch in arrival order: is_new[i] = 1 iff Sig i is neither
+ * in the set nor at an earlier row of the batch -- the rows whose programs are
+ * appended to fuzzer.corpus.  Afterwards the set holds the union.  A NULL *s is
+ * allocated only if n > 0.  All or nothing: the new storage is allocated
+ * before d_is_new is written, and the set takes it last. */
+int syzsig_sigset_add_dev(syzsig_ctx* ctx, syzsig_sigset** s, const uint8_t* d_sig, uint64_t n, uint8_t* d_is_new);
+/* in[i] = 1 iff Sig i is in s (NULL: the empty set). */
+int syzsig_sigset_contains_dev(syzsig_ctx* ctx, const syzsig_sigset* s, const uint8_t* d_sig, uint64_t n,
+                               uint8_t* d_in);
+/* The set's Sigs ascending (one fixed instance of Go's map order, as
+ * Serialize's elsewhere); *n_out = Len.  cap (in Sigs) below it: SYZSIG_ERANGE,
+ * nothing written. */
+int syzsig_sigset_export_dev(syzsig_ctx* ctx, const syzsig_sigset* s, uint8_t* d_sig, uint64_t cap, uint64_t* n_out);
+/* The dense keys syzsig_manager_new_input_batch takes for hash.String(a.Prog):
+ * key[i] = the number of distinct Sigs whose first row precedes Sig i's first
+ * row (dense, in order of first appearance), first[k] = key k's first row,
+ * known[k] = 1 iff key k's Sig is in `known` (the keys of mgr.corpus; NULL:
+ * empty): the keys whose old entry goes in as a SYZSIG_INPUT_PRESENT row.
+ * *nkeys = the distinct Sigs.  d_key has n entries, d_first and d_known n
+ * entries of capacity. */
+int syzsig_number_sigs_dev(syzsig_ctx* ctx, const syzsig_sigset* known, const uint8_t* d_sig, uint64_t n,
+                           uint32_t* d_key, uint32_t* d_first, uint8_t* d_known, uint64_t* nkeys);
+/* hubSync's diff (manager.go:1142-1158) with d_sig the Sigs of mgr.corpus:
+ * add[i] = 1 iff Sig i is not in hubCorpus and at no earlier row (:1146-1150);
+ * d_del_sig receives, ascending, the Sigs of hubCorpus absent from the batch
+ * (:1152-1157), *ndel their number; afterwards hubCorpus is the set of the
+ * batch.  del_cap (in Sigs) below *ndel: SYZSIG_ERANGE with *ndel set and
+ * nothing else changed.  On a NULL *hub_corpus this is the Connect branch
+ * (:1110-1113): every first row is added; it stays NULL when n == 0. */
+int syzsig_hub_sync_dev(syzsig_ctx* ctx, syzsig_sigset** hub_corpus, const uint8_t* d_sig, uint64_t n,
+                        uint8_t* d_add, uint8_t* d_del_sig, uint64_t del_cap, uint64_t* ndel);
 
 /* ---- hash-sharded maxSignal across GPUs (one process per GPU) ----
  * The batch is split by program range over G GPUs (serial order = GPU-major);

@@ -36,6 +36,11 @@ SYZSIG_SEG_INPUT = 1  # ... the Signal of one of its NewInputs (fuzzer.go:348-35
 SYZSIG_INPUT_PRESENT = 1  # a NewInput batch row that is the key's old corpus entry
 SYZSIG_HINT_LIST = 1024  # the per-arg candidate list of syzsig_hint_mutants_dev in LDS (hints.hip)
 SYZSIG_HINT_MAX_DATA = 100  # prog/hints.go:38 maxDataLength
+SYZSIG_SIG_BYTES = 20  # hash.Sig, pkg/hash/hash.go:14
+SYZSIG_HASH_MAX_MSG = 1 << 28  # syzsig_hash_dev: the longest message
+SYZSIG_HASH_STAGE = 32768  # ... a wave's span up to this is staged in LDS (sigs.hip)
+SYZSIG_HASH_LONG = 4096  # ... a message past this goes to the second launch
+SYZSIG_SIGSET_TILE = 2048  # the sort tile of a batch of Sigs (sigs.hip)
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
 SYZSIG_INGEST_ECOMPTYPE = 9
@@ -163,6 +168,16 @@ SIGNATURES = {
     "syzsig_hint_mutants_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, _P, _P, _P, _P, c_uint64, c_uint64, _P,
                                         c_uint32, _P, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     "syzsig_hint_mutants_stats": (c_int, [_P, _P]),
+    "syzsig_hash_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P]),
+    "syzsig_hash_stats": (c_int, [_P, _P]),
+    "syzsig_sigset_make": (c_int, [_P, _PP]),
+    "syzsig_sigset_free": (None, [_P]),
+    "syzsig_sigset_len": (c_uint64, [_P]),
+    "syzsig_sigset_add_dev": (c_int, [_P, _PP, _P, c_uint64, _P]),
+    "syzsig_sigset_contains_dev": (c_int, [_P, _P, _P, c_uint64, _P]),
+    "syzsig_sigset_export_dev": (c_int, [_P, _P, _P, c_uint64, POINTER(c_uint64)]),
+    "syzsig_number_sigs_dev": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, POINTER(c_uint64)]),
+    "syzsig_hub_sync_dev": (c_int, [_P, _PP, _P, c_uint64, _P, _P, c_uint64, POINTER(c_uint64)]),
     "syzsig_ingest_exec_output_dev": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P, _P, _P, _P,
                                               _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_triage_records_dev": (c_int, [_P, _P, _PP, _P, c_uint64, _P, c_uint32, _P,

@@ -192,7 +192,14 @@ enum WsSlot : int {
 	kWsHmMeta = 64,
 	kWsHmStage = 65,
 	kWsHmQuery = 66,
-	kWsCount = 67,
+	// sigs.hip: the long messages' list | a batch of Sigs: its keys and the merge's other buffer, the
+	// flags / ranks / tile table, the outputs held back until the commit
+	kWsHashList = 67,
+	kWsSgBufA = 68,
+	kWsSgBufB = 69,
+	kWsSgMeta = 70,
+	kWsSgOut = 71,
+	kWsCount = 72,
 };
 
 // the debug flags that change only the path taken, never a result
@@ -255,6 +262,8 @@ struct syzsig_ctx {
 	uint64_t it_stats[4] = {0, 0, 0, 0};  // syzsig_triage_items_stats: the last triage_items call's paths (items.hip)
 	uint64_t pr_stats[4] = {0, 0, 0, 0};  // syzsig_poll_res_stats: the last fuzzer_poll_res call's paths (pollres.hip)
 	uint64_t hm_stats[4] = {0, 0, 0, 0};  // syzsig_hint_mutants_stats: the last hint_mutants call's paths (hints.hip)
+	uint64_t hs_stats[4] = {0, 0, 0, 0};  // syzsig_hash_stats: the last hash call's paths (sigs.hip)
+	bool hash_stage = true;               // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
 };
 
 struct syzsig_set {
