@@ -64,7 +64,8 @@ int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
  * stream work of the last syzsig_manager_poll_batch, syzsig_edge_cover_dev,
  * syzsig_triage_cover_dev, syzsig_triage_items_dev, syzsig_exec_comps_dev,
  * syzsig_comp_map_dev, syzsig_shrink_expand_dev, syzsig_hint_mutants_dev, syzsig_hash_dev or
- * syzsig_sigset_add_dev call (uploads / first kernel to its last kernel,
+ * syzsig_sigset_add_dev call, or of the last syzsig_calc_prios_dev, syzsig_static_prio_finish_dev,
+ * syzsig_choice_table_dev or syzsig_choice_lookup_dev call (uploads / first kernel to its last kernel,
  * including the host round trips between); for syzsig_manager_new_input_batch
  * the host wall time of the call, which ends synchronised. */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
@@ -791,6 +792,61 @@ int syzsig_number_sigs_dev(syzsig_ctx* ctx, const syzsig_sigset* known, const ui
  * (:1110-1113): every first row is added; it stays NULL when n == 0. */
 int syzsig_hub_sync_dev(syzsig_ctx* ctx, syzsig_sigset** hub_corpus, const uint8_t* d_sig, uint64_t n,
                         uint8_t* d_add, uint8_t* d_del_sig, uint64_t del_cap, uint64_t* ndel);
+
+/* ---- prog/prio.go:133-245: call-to-call priorities over the whole corpus and
+ * the ChoiceTable (the numeric part; the program model stays with the caller) ----
+ * N = len(target.Syscalls); a matrix is N * N row-major.  Every result is what
+ * the reference computes on amd64, bit for bit: float32, each operation rounded
+ * on its own (no fused multiply-add), IEEE division.
+ * SYZSIG_PRIO_MAX_CALLS: one row of u32 counters is static LDS.
+ * SYZSIG_PRIO_SPLIT: the default of `split` below. */
+#define SYZSIG_PRIO_MAX_CALLS 16384
+#define SYZSIG_PRIO_SPLIT 4096
+/* calcDynamicPrio and CalculatePriorities' product (prio.go:133-149, :27-36;
+ * manager.go:896 on Connect).  The corpus is CSR: program p's calls are
+ * d_call_id[off[p] .. off[p + 1]) (d_prog_off has nprog + 1 entries, off[0] = 0,
+ * off[nprog] = total), each the call's Meta.ID.  d_prios[a * N + b] = the
+ * normalised count of ordered pairs of positions (a at one, b at the other) over
+ * all programs -- a cell is min(count, 2^24) as a float32 `+= 1.0` leaves it --
+ * times d_static[a * N + b] when d_static is given (NULL: the dynamic matrix
+ * alone).  A row whose cells are all equal and non-zero is NaN throughout, as in
+ * Go.  split: a call that occurs more than `split` times has its row counted in
+ * slices of `split` occurrences by workgroups of their own (0 = the default; it
+ * is raised when the slices' partial rows would pass 1 GB); no result depends
+ * on it.
+ * SYZSIG_EINVAL: a NULL argument, N = 0, offsets that decrease or do not run
+ * from 0 to total, a call id >= N (Go panics on the index).  SYZSIG_ERANGE:
+ * N > SYZSIG_PRIO_MAX_CALLS; the sum of len_p^2 over the programs is 2^32 or
+ * more (u32 counters are exact below it).  Both are found before any counting
+ * and before d_prios is written. */
+int syzsig_calc_prios_dev(syzsig_ctx* ctx, const uint64_t* d_prog_off, const uint32_t* d_call_id, uint64_t nprog,
+                          uint64_t total, uint64_t N, uint64_t split, const float* d_static, float* d_prios);
+/* The tail of calcStaticPriorities (prio.go:118-129) in place on the summed
+ * matrix: pp[c0] = the row's max (over the row as given: the reference leaves
+ * the diagonal 0 until here), then normalizePrio. */
+int syzsig_static_prio_finish_dev(syzsig_ctx* ctx, float* d_prios, uint64_t N);
+/* BuildChoiceTable (prio.go:198-228; syz-fuzzer/fuzzer.go:173).  d_enabled:
+ * u8[N], non-zero = enabled (NULL: every call).  For an enabled row i,
+ * d_run[i * N + j] = the sum over enabled j' <= j of int(prios[i][j'] * 1000)
+ * (1 when d_prios is NULL, Go's nil prios); a disabled row, nil in Go, is zeros.
+ * int() of a NaN, of a negative value or of one that is 2^31 / N or more is not
+ * defined by Go: such a weight at an enabled row and column is SYZSIG_EINVAL,
+ * syzsig_last_error names the first such row, and d_run is not written. */
+int syzsig_choice_table_dev(syzsig_ctx* ctx, const float* d_prios, const uint8_t* d_enabled, uint64_t N,
+                            int32_t* d_run);
+/* Choose's lookup (prio.go:230-245; prog/rand.go:398) for n queries:
+ * out[q] = sort.SearchInts(run[call[q]], x[q]), the smallest i with
+ * run[call][i] >= x.  With x in [1, run[call][N - 1]], what r.Intn(total) + 1
+ * draws, that is an enabled call of non-zero weight, so the reference's loop
+ * never retries.  call < 0 or a row whose total is 0 (disabled): out[q] = N,
+ * "uniform over enabledCalls", which is the caller's draw.  SYZSIG_EINVAL,
+ * nothing written: a call >= N, an x outside [1, total] of an enabled row. */
+int syzsig_choice_lookup_dev(syzsig_ctx* ctx, const int32_t* d_run, uint64_t N, const int32_t* d_call,
+                             const int32_t* d_x, uint64_t n, int32_t* d_out);
+/* The paths of the last syzsig_calc_prios_dev call: out[0] = rows counted whole,
+ * out[1] = rows split, out[2] = slices, out[3] = pair increments (the sum of
+ * len_p^2). */
+int syzsig_prio_stats(syzsig_ctx* ctx, uint64_t out[4]);
 
 /* ---- hash-sharded maxSignal across GPUs (one process per GPU) ----
  * The batch is split by program range over G GPUs (serial order = GPU-major);

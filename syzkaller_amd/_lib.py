@@ -41,6 +41,8 @@ SYZSIG_HASH_MAX_MSG = 1 << 28  # syzsig_hash_dev: the longest message
 SYZSIG_HASH_STAGE = 32768  # ... a wave's span up to this is staged in LDS (sigs.hip)
 SYZSIG_HASH_LONG = 4096  # ... a message past this goes to the second launch
 SYZSIG_SIGSET_TILE = 2048  # the sort tile of a batch of Sigs (sigs.hip)
+SYZSIG_PRIO_MAX_CALLS = 16384  # syzsig_calc_prios_dev: len(target.Syscalls) at most (one LDS row, prio.hip)
+SYZSIG_PRIO_SPLIT = 4096  # ... a call with more occurrences has its row counted in slices
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
 SYZSIG_INGEST_ECOMPTYPE = 9
@@ -178,6 +180,11 @@ SIGNATURES = {
     "syzsig_sigset_export_dev": (c_int, [_P, _P, _P, c_uint64, POINTER(c_uint64)]),
     "syzsig_number_sigs_dev": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_hub_sync_dev": (c_int, [_P, _PP, _P, c_uint64, _P, _P, c_uint64, POINTER(c_uint64)]),
+    "syzsig_calc_prios_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, c_uint64, c_uint64, _P, _P]),
+    "syzsig_static_prio_finish_dev": (c_int, [_P, _P, c_uint64]),
+    "syzsig_choice_table_dev": (c_int, [_P, _P, _P, c_uint64, _P]),
+    "syzsig_choice_lookup_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P]),
+    "syzsig_prio_stats": (c_int, [_P, _P]),
     "syzsig_ingest_exec_output_dev": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P, _P, _P, _P,
                                               _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_triage_records_dev": (c_int, [_P, _P, _PP, _P, c_uint64, _P, c_uint32, _P,

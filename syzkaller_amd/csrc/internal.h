@@ -199,7 +199,11 @@ enum WsSlot : int {
 	kWsSgBufB = 69,
 	kWsSgMeta = 70,
 	kWsSgOut = 71,
-	kWsCount = 72,
+	// prio.hip: the histogram, offsets, cursors and slice plan | the postings | the slices' partial rows
+	kWsPqMeta = 72,
+	kWsPqPost = 73,
+	kWsPqPart = 74,
+	kWsCount = 75,
 };
 
 // the debug flags that change only the path taken, never a result
@@ -263,6 +267,7 @@ struct syzsig_ctx {
 	uint64_t pr_stats[4] = {0, 0, 0, 0};  // syzsig_poll_res_stats: the last fuzzer_poll_res call's paths (pollres.hip)
 	uint64_t hm_stats[4] = {0, 0, 0, 0};  // syzsig_hint_mutants_stats: the last hint_mutants call's paths (hints.hip)
 	uint64_t hs_stats[4] = {0, 0, 0, 0};  // syzsig_hash_stats: the last hash call's paths (sigs.hip)
+	uint64_t pq_stats[4] = {0, 0, 0, 0};  // syzsig_prio_stats: the last calc_prios call's paths (prio.hip)
 	bool hash_stage = true;               // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
 };
 

@@ -276,6 +276,32 @@ class Device:
         check(self.L.syzsig_hint_mutants_stats(self.eng.h, out))
         return tuple(int(x) for x in out)
 
+    # ---------------------------------------------------------------- call priorities and the choice table
+    def calculate_priorities(self, corpus_ids, ncalls, static=None, split=0, out=None):
+        """target.CalculatePriorities(corpus), prog/prio.go:27-36, over the
+        calls' ids of every corpus program: float32[N, N] on the device
+        (syzkaller_amd.prio.calculate_priorities)."""
+        from . import prio
+        return prio.calculate_priorities(self, corpus_ids, ncalls, static, split, out)
+
+    def prio_stats(self):
+        """(rows counted whole, rows split, slices, pair increments) of the
+        last calculate_priorities (syzsig_prio_stats)."""
+        from . import prio
+        return prio.prio_stats(self)
+
+    def static_finish(self, mat):
+        """The tail of calcStaticPriorities, prog/prio.go:118-129
+        (syzkaller_amd.prio.static_finish)."""
+        from . import prio
+        return prio.static_finish(self, mat)
+
+    def choice_table(self, prios, enabled, ncalls):
+        """target.BuildChoiceTable(prios, enabled), prog/prio.go:198-228: a
+        syzkaller_amd.prio.ChoiceTable."""
+        from . import prio
+        return prio.ChoiceTable.build(self, prios, enabled, ncalls)
+
     # ---------------------------------------------------------------- executor output ingest
     def ingest_exec_output(self, out, prog_off, prog_call, call_any, call_num=None, want_cover=False):
         """pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output
