@@ -65,7 +65,8 @@ int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
  * syzsig_triage_cover_dev, syzsig_triage_items_dev, syzsig_exec_comps_dev,
  * syzsig_comp_map_dev, syzsig_shrink_expand_dev, syzsig_hint_mutants_dev, syzsig_hash_dev or
  * syzsig_sigset_add_dev call, or of the last syzsig_calc_prios_dev, syzsig_static_prio_finish_dev,
- * syzsig_choice_table_dev or syzsig_choice_lookup_dev call (uploads / first kernel to its last kernel,
+ * syzsig_choice_table_dev, syzsig_choice_lookup_dev, syzsig_call_cover_dev, syzsig_report_pcs_dev or
+ * syzsig_uncovered_pcs_dev call (uploads / first kernel to its last kernel,
  * including the host round trips between); for syzsig_manager_new_input_batch
  * the host wall time of the call, which ends synchronised. */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
@@ -847,6 +848,64 @@ int syzsig_choice_lookup_dev(syzsig_ctx* ctx, const int32_t* d_run, uint64_t N, 
  * out[1] = rows split, out[2] = slices, out[3] = pair increments (the sum of
  * len_p^2). */
 int syzsig_prio_stats(syzsig_ctx* ctx, uint64_t out[4]);
+
+/* ---- syz-manager/html.go, syz-manager/cover.go: the corpus-wide loops behind
+ * the manager's coverage pages, their numeric part.  The text tools (objdump,
+ * nm, readelf, addr2line, the source files, the HTML template) stay with the
+ * caller, who interns call names to dense ids.  Every array is device memory;
+ * each call is all-or-nothing on an argument error, with outputs untouched.
+ *
+ * collectSyscallInfo (html.go:135-149) and httpCover's selection
+ * (html.go:202-212).  The corpus as CSR: input i's Cover is d_cov[d_cov_off[i]
+ * .. d_cov_off[i + 1]) (offsets from 0 to total; repeats allowed within and
+ * across inputs), its call d_call[i] < ncalls.  d_select: NULL = every input,
+ * else input i takes part iff d_select[i] != 0.  Outputs: d_count[c] = the
+ * selected inputs of call c (an input with an empty cover counts);
+ * d_cover_len[c] = len(cc.cov); the unions as CSR, call c's PCs ascending and
+ * distinct at d_call_cov[d_call_cov_off[c] .. d_call_cov_off[c + 1]) (ncalls +
+ * 1 offsets).  d_all_cov / n_all (both or neither): the union over all
+ * selected inputs, ascending, and its size -- httpCover with call == "",
+ * httpRawCover; room for cover_cap PCs as well.  cover_cap below the selected
+ * inputs' total PCs is SYZSIG_ERANGE (that total always suffices), a call id
+ * >= ncalls or offsets that decrease or do not run from 0 to total
+ * SYZSIG_EINVAL, both checked before anything is written.  total < 2^31. */
+int syzsig_call_cover_dev(syzsig_ctx* ctx, const uint64_t* d_cov_off, const uint32_t* d_cov, uint64_t ninputs,
+                          uint64_t total, const uint32_t* d_call, const uint8_t* d_select, uint64_t ncalls,
+                          uint32_t* d_count, uint32_t* d_cover_len, uint64_t* d_call_cov_off, uint32_t* d_call_cov,
+                          uint64_t cover_cap, uint32_t* d_all_cov, uint64_t* n_all);
+/* cover.RestorePC (pkg/cover/cover.go:28-30), previousInstructionPC
+ * (cover.go:394-411) and httpRawCover's sort (html.go:323-331) over n PCs:
+ * d_out_order[i] = prev(base << 32 + d_pcs[i]) (generateCoverHTML's pcs,
+ * cover.go:99-104), d_out_sorted = the same values ascending.  Repeats stay
+ * (on arm two PCs can share a previous PC); with base == 0 a PC below the
+ * subtrahend wraps as Go's u64 does and sorts last.  An arch other than the
+ * five below is SYZSIG_EINVAL (Go panics).  n < 2^31. */
+#define SYZSIG_ARCH_AMD64 0u   /* pc - 5 */
+#define SYZSIG_ARCH_386 1u     /* pc - 1 */
+#define SYZSIG_ARCH_ARM64 2u   /* pc - 4 */
+#define SYZSIG_ARCH_ARM 3u     /* (pc - 3) & ~1 */
+#define SYZSIG_ARCH_PPC64LE 4u /* pc - 4 */
+int syzsig_report_pcs_dev(syzsig_ctx* ctx, const uint32_t* d_pcs, uint64_t n, uint32_t base, uint32_t arch,
+                          uint64_t* d_out_order, uint64_t* d_out_sorted);
+/* uncoveredPcsInFuncs (cover.go:254-304) for d_pcs in the order the loop sees
+ * them.  Symbols as d_sym_start / d_sym_end (end = Addr + Size), sorted by
+ * start as sort.Sort(symbols) leaves them (equal starts in the caller's
+ * order); d_all_cover = allCoverPCs strictly ascending (a repeat is
+ * SYZSIG_EINVAL: drop them first, the result is a map's keys).  d_out (room for
+ * nall PCs) = the keys of `uncovered` ascending, *n_out their count.  nall == 0
+ * gives an empty result (cover.go:268).  The device runs sort.Search's probe
+ * sequence over `pc < end` (ends need not be monotone), keys handledFuncs by
+ * start with the end of the alias that the first PC found, and adds a
+ * function's sites at the position of its first PC, before that position's
+ * delete.  npc, nsym, nall < 2^32. */
+int syzsig_uncovered_pcs_dev(syzsig_ctx* ctx, const uint64_t* d_sym_start, const uint64_t* d_sym_end, uint64_t nsym,
+                             const uint64_t* d_all_cover, uint64_t nall, const uint64_t* d_pcs, uint64_t npc,
+                             uint64_t* d_out, uint64_t* n_out);
+/* The paths of the context's last call of the three above (tests, tuning):
+ * out[0] = call segments of more than SYZSIG_COVER_TILE PCs (repeats
+ * included), out[1] = the rank-merge passes over them, out[2] = functions
+ * handled, out[3] = those whose site range was walked by a workgroup. */
+int syzsig_report_stats(syzsig_ctx* ctx, uint64_t out[4]);
 
 /* ---- hash-sharded maxSignal across GPUs (one process per GPU) ----
  * The batch is split by program range over G GPUs (serial order = GPU-major);

@@ -203,7 +203,12 @@ enum WsSlot : int {
 	kWsPqMeta = 72,
 	kWsPqPost = 73,
 	kWsPqPart = 74,
-	kWsCount = 75,
+	// report.hip: a call's counts, offsets and cursors; the PCs in call order | the keys of report_pcs;
+	// the sorted survivors before the gather | uncovered_pcs' add / del words and block counts
+	kWsRcMeta = 75,
+	kWsRcStage = 76,
+	kWsRcStage2 = 77,
+	kWsCount = 78,
 };
 
 // the debug flags that change only the path taken, never a result
@@ -268,7 +273,8 @@ struct syzsig_ctx {
 	uint64_t hm_stats[4] = {0, 0, 0, 0};  // syzsig_hint_mutants_stats: the last hint_mutants call's paths (hints.hip)
 	uint64_t hs_stats[4] = {0, 0, 0, 0};  // syzsig_hash_stats: the last hash call's paths (sigs.hip)
 	uint64_t pq_stats[4] = {0, 0, 0, 0};  // syzsig_prio_stats: the last calc_prios call's paths (prio.hip)
-	bool hash_stage = true;               // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
+	uint64_t rc_stats[4] = {0, 0, 0, 0};  // syzsig_report_stats: the last coverage-report call's paths (report.hip)
+	bool hash_stage = true;              // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
 };
 
 struct syzsig_set {

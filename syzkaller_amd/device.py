@@ -302,6 +302,42 @@ class Device:
         from . import prio
         return prio.ChoiceTable.build(self, prios, enabled, ncalls)
 
+    # ---------------------------------------------------------------- the manager's coverage pages
+    def report_corpus(self, inputs, calls=()):
+        """mgr.corpus as the report kernels read it (syzkaller_amd.report.Corpus):
+        inputs = {sig: (call name, cover u32[])}."""
+        from . import report
+        return report.Corpus(self, inputs, calls)
+
+    def syscall_info(self, corpus):
+        """collectSyscallInfo, syz-manager/html.go:135-149: {call: (count,
+        len(cov))} (syzkaller_amd.report.syscall_info)."""
+        from . import report
+        return report.syscall_info(corpus)
+
+    def cover_for(self, corpus, call=None, input=None):
+        """httpCover's cov, syz-manager/html.go:202-212, as a Cover
+        (syzkaller_amd.report.cover_for)."""
+        from . import report
+        return report.cover_for(corpus, call, input)
+
+    def report_pcs(self, pcs, base, arch):
+        """RestorePC + previousInstructionPC per PC, in input order and sorted
+        (syzkaller_amd.report.report_pcs)."""
+        from . import report
+        return report.report_pcs(self, pcs, base, arch)
+
+    def uncovered_pcs(self, sym_start, sym_end, all_cover, pcs):
+        """uncoveredPcsInFuncs, syz-manager/cover.go:254-304, for pcs in the
+        order given (syzkaller_amd.report.uncovered_pcs)."""
+        from . import report
+        return report.uncovered_pcs(self, sym_start, sym_end, all_cover, pcs)
+
+    def report_stats(self):
+        """The paths of the last report call (syzsig_report_stats)."""
+        from . import report
+        return report.report_stats(self)
+
     # ---------------------------------------------------------------- executor output ingest
     def ingest_exec_output(self, out, prog_off, prog_call, call_any, call_num=None, want_cover=False):
         """pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output
