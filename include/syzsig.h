@@ -445,6 +445,44 @@ int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uint64_t npc, 
                           const uint32_t* d_call_len, uint64_t ncalls, const uint32_t* d_prog_call, uint64_t nprog,
                           const uint32_t* d_completed, uint32_t flags, uint32_t* d_cover, uint32_t* d_cover_cnt);
 
+/* ---- the KCOV target of the two functions above ----
+ * The reference instantiates write_coverage_signal<cover_t> twice
+ * (executor.h:595-598): <uint64> for a 64-bit kernel and <uint32> for a 32-bit
+ * one (KCOV_INIT_TRACE32, executor_linux.cc:143-146, :255-275), and its
+ * cover_check is the x86 text range only for a uint64 PC in a Linux executor
+ * built for i386 / x86_64 (executor_linux.cc:196-204); cover_check(uint32), and
+ * cover_check(uint64) of every other build (arm64, ppc64le, executor_bsd.cc:
+ * 223-231, executor_fuchsia.cc:59-67, akaros, windows) is `return true`.
+ * `target` names one of those three:
+ *   0                          u64 PCs, no check;
+ *   SYZSIG_TARGET_PC32         u32 PCs (d_pcs is const uint32_t*, npc and
+ *                              call_start count u32 words), no check;
+ *   SYZSIG_TARGET_CHECK_X86    u64 PCs, the x86 range: syzsig_edge_derive_dev
+ *                              and syzsig_edge_cover_dev (= SYZSIG_TARGET_LINUX_AMD64).
+ * SYZSIG_TARGET_PC32 | SYZSIG_TARGET_CHECK_X86 (the reference has no such
+ * executor) and any other bit are SYZSIG_EINVAL, nothing written.  Every other
+ * argument, limit and result is that of the function without `_target`.
+ * Signals depend on a PC's low 32 bits only (hash, dedup and write_output take
+ * uint32), so the three targets differ in what is loaded and in whether a PC
+ * can abort its program.  The cover output differs more with
+ * SYZSIG_COVER_DEDUP: std::sort + std::unique run on cover_t (executor.h:
+ * 518-522) before the truncation, so under target 0 the u32 output is ordered
+ * by the u64 PCs and holds a low word once per distinct u64 PC (PCs
+ * 0x100000009, 0x200000003 give 9, 3); under SYZSIG_TARGET_PC32 it is the
+ * ascending distinct u32 PCs; under SYZSIG_TARGET_CHECK_X86 every upper word is
+ * 0xffffffff and the two coincide. */
+#define SYZSIG_TARGET_PC32 1u
+#define SYZSIG_TARGET_CHECK_X86 2u
+#define SYZSIG_TARGET_LINUX_AMD64 SYZSIG_TARGET_CHECK_X86
+int syzsig_edge_derive_target_dev(syzsig_ctx* ctx, const void* d_pcs, uint64_t npc, const uint64_t* d_call_start,
+                                  const uint32_t* d_call_len, uint64_t ncalls, const uint32_t* d_prog_call,
+                                  uint64_t nprog, uint32_t target, uint32_t* d_sigs, uint32_t* d_sig_cnt,
+                                  uint32_t* d_completed);
+int syzsig_edge_cover_target_dev(syzsig_ctx* ctx, const void* d_pcs, uint64_t npc, const uint64_t* d_call_start,
+                                 const uint32_t* d_call_len, uint64_t ncalls, const uint32_t* d_prog_call,
+                                 uint64_t nprog, const uint32_t* d_completed, uint32_t flags, uint32_t target,
+                                 uint32_t* d_cover, uint32_t* d_cover_cnt);
+
 /* ---- syz-fuzzer/proc.go:139 inputCover.Merge(inf.Cover) and :173 Cover:
  * inputCover.Serialize(), over the item / run layout of syzsig_triage_runs_dev ----
  * Run r = i * runs + k of item i has the cover list d_cover[run_cover_start[r]

@@ -6,6 +6,7 @@ include/syzsig.h).  This package is its Python host side:
   device  -- the batch path over device tensors (triage, edge derivation,
              minimize, shard routing)
   dist    -- hash-sharded maxSignal over one process per GPU
+  targets -- the KCOV target of a kernel under test (PC width, cover_check)
   synth   -- host-side synthetic KCOV workload (same generator as on device)
 """
 from ._lib import LIB_PATH, SyzsigError, CorruptedSerial  # noqa: F401

@@ -26,6 +26,10 @@ SYZSIG_DEBUG_EDGE_PASSES = 2048
 SYZSIG_DEBUG_POLL_FAIL = 4096
 SYZSIG_DEBUG_AGG_IDX64 = 8192
 SYZSIG_COVER_DEDUP = 1
+# the KCOV target of syzsig_edge_derive_target_dev / syzsig_edge_cover_target_dev (syzkaller_amd/targets.py)
+SYZSIG_TARGET_PC32 = 1  # cover_t = uint32: the trace holds u32 PCs
+SYZSIG_TARGET_CHECK_X86 = 2  # cover_check(uint64) = the x86 text range
+SYZSIG_TARGET_LINUX_AMD64 = SYZSIG_TARGET_CHECK_X86  # what the entry points without `_target` run
 SYZSIG_COVER_TILE = 4096  # include/syzsig.h: longer segments leave the one-workgroup LDS sort
 SYZSIG_COMPS_TILE = 2048  # the same for the comparison hints' keys (comps.hip)
 SYZSIG_CORPUS_TILE = 2048  # the same for a corpus key's entries in the NewInput batch (corpus.hip)
@@ -156,6 +160,9 @@ SIGNATURES = {
     "syzsig_triage_batch": (c_int, [_P, _P, _PP, POINTER(Batch), POINTER(BatchStats)]),
     "syzsig_edge_derive_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, _P, _P]),
     "syzsig_edge_cover_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, c_uint32, _P, _P]),
+    "syzsig_edge_derive_target_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, c_uint32, _P, _P, _P]),
+    "syzsig_edge_cover_target_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, c_uint32, c_uint32, _P,
+                                             _P]),
     "syzsig_triage_cover_dev": (c_int, [_P, c_uint64, c_uint32, _P, _P, _P, _P, _P, _P, c_uint64, _P, _P, _P, _P,
                                         c_uint64, POINTER(c_uint64)]),
     "syzsig_triage_items_dev": (c_int, [_P, _P, c_uint64, _P, _P, _P, c_uint64, _P, _P, _P, _P, c_uint64, _P, _P, c_uint64,

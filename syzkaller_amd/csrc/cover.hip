@@ -12,16 +12,27 @@
 // cover lists of an item's merged runs): sort ascending, drop equal
 // neighbours, write the survivors densely and their count.
 //
-// Exactness of sorting the low words.  Every PC of a completed call passed
-// cover_check (executor_linux.cc:196-204), so it lies in [0xffffffff80000000,
-// 0xffffffffff000000): its upper word is 0xffffffff.  u64 order and equality
-// of such PCs are those of their low words, so sort + unique on the low words,
-// which is what leaves here, is the reference's sort + unique on u64 followed
-// by the truncation of executor.h:519-526.  A call that did not complete
-// (the one holding the PC that failed cover_check, and every later call of its
-// program) never reaches this: its segment length is forced to 0 from
-// `completed` before any key is read (k_cover_prep_calls), as doexit(0)
-// happens inside the signal loop before any cover is written.
+// The keys, per KCOV target (syzsig.h SYZSIG_TARGET_*; std::sort + std::unique
+// run on cover_t, the truncation of executor.h:525-526 comes after):
+//   SYZSIG_TARGET_CHECK_X86 -- the low words of the u64 PCs.  Exactness of
+//     sorting the low words holds for this target and for it alone: every PC of
+//     a completed call passed cover_check (executor_linux.cc:196-204), so it
+//     lies in [0xffffffff80000000, 0xffffffffff000000): its upper word is
+//     0xffffffff.  u64 order and equality of such PCs are those of their low
+//     words, so sort + unique on the low words, which is what leaves here, is
+//     the reference's sort + unique on u64 followed by the truncation.
+//   SYZSIG_TARGET_PC32 -- the u32 PCs themselves (cover_t = uint32): the same
+//     u32 sort, loaded 4 B per key.
+//   0 (u64, no check) -- the full u64 PCs.  Upper words differ, so two PCs
+//     with one low word both survive and the output follows the u64 order:
+//     0x100000009, 0x200000003 leave as 9, 3.  Sorted as u64 keys (CvTile64:
+//     segsort.h's plain one-word tile), the survivors truncated on the way out
+//     (CvOutLow).
+// A call that did not complete (the one holding the PC that failed
+// cover_check, and every later call of its program) never reaches this: its
+// segment length is forced to 0 from `completed` before any key is read
+// (k_cover_prep_calls), as doexit(0) happens inside the signal loop before any
+// cover is written.
 //
 // The segmented sort-unique is segsort.h's, over u32 keys with the tile
 // routines of cover_tile.h (shared with report.hip; T = kCvTile keys,
@@ -44,6 +55,7 @@
 #include <algorithm>
 
 #include "cover_tile.h"
+#include "edge_args.h"
 
 namespace syz {
 
@@ -59,7 +71,7 @@ __global__ __launch_bounds__(64) void k_cover_prep_calls(const uint64_t* __restr
 	uint64_t err = 0, nl = 0, nt = 0, nk = 0;
 	for (uint64_t p = blockIdx.x; p < nprog; p += gridDim.x) {
 		const uint64_t cb = prog_call[p], ce = prog_call[p + 1];
-		if (cb > ce || ce > ncalls || completed[p] > ce - cb) {
+		if (edge_prog_bad(cb, ce, ncalls) || completed[p] > ce - cb) {
 			err += threadIdx.x == 0;
 			continue;
 		}
@@ -67,7 +79,7 @@ __global__ __launch_bounds__(64) void k_cover_prep_calls(const uint64_t* __restr
 		for (uint64_t c = cb + threadIdx.x; c < ce; c += blockDim.x) {
 			const uint64_t start = call_start[c];
 			const uint32_t len = call_len[c];
-			if (len >= kCoverSize || start > npc || len > npc - start) {
+			if (edge_call_bad(start, len, npc)) {
 				err++;  // executor_linux.cc:186-187 fail("too much cover") / malformed input
 				continue;
 			}
@@ -125,7 +137,9 @@ __global__ __launch_bounds__(256) void k_cover_prep_items(
 }
 
 // executor.h:525-527 without flag_dedup_cover: the PCs truncated, in trace order
-__global__ __launch_bounds__(kCvThreads) void k_cover_trunc(const uint64_t* __restrict__ pcs, SuSegs S, CvOut pol)
+// (PC = cover_t; a copy for u32 PCs)
+template <typename PC>
+__global__ __launch_bounds__(kCvThreads) void k_cover_trunc(const PC* __restrict__ pcs, SuSegs S, CvOut pol)
 {
 	for (uint64_t seg = blockIdx.x; seg < S.nseg; seg += gridDim.x) {
 		const uint32_t n = S.seg_len[seg];
@@ -142,17 +156,16 @@ __global__ __launch_bounds__(kCvThreads) void k_cover_trunc(const uint64_t* __re
 
 using namespace syz;
 
-extern "C" int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uint64_t npc,
-                                     const uint64_t* d_call_start, const uint32_t* d_call_len, uint64_t ncalls,
-                                     const uint32_t* d_prog_call, uint64_t nprog, const uint32_t* d_completed,
-                                     uint32_t flags, uint32_t* d_cover, uint32_t* d_cover_cnt)
+extern "C" int syzsig_edge_cover_target_dev(syzsig_ctx* ctx, const void* d_pcs, uint64_t npc,
+                                            const uint64_t* d_call_start, const uint32_t* d_call_len, uint64_t ncalls,
+                                            const uint32_t* d_prog_call, uint64_t nprog, const uint32_t* d_completed,
+                                            uint32_t flags, uint32_t target, uint32_t* d_cover, uint32_t* d_cover_cnt)
 {
 	SYZ_LOCK(ctx);
-	if (!ctx || (nprog && (!d_prog_call || !d_completed)) || (ncalls && (!d_call_start || !d_call_len || !d_cover_cnt)) ||
-	    (npc && (!d_pcs || !d_cover)))
-		return fail(SYZSIG_EINVAL, "edge_cover: NULL argument");
-	if (flags & ~(uint32_t)SYZSIG_COVER_DEDUP)
-		return fail(SYZSIG_EINVAL, "edge_cover: unknown flag");
+	const EdgeStatus a = edge_cover_args(ctx, d_pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog,
+	                                     d_completed, flags, target, d_cover, d_cover_cnt);
+	if (a.code != SYZSIG_OK)
+		return fail(a.code, a.msg);
 	if (ncalls == 0)
 		return SYZSIG_OK;
 	const hipStream_t s = ctx->stream;
@@ -172,10 +185,20 @@ extern "C" int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uin
 		                           "a call with >= 262144 PCs");
 	const SuSegs S{d_pcs, 1, d_call_start, (const uint32_t*)seg_len, 1, (const uint32_t*)seg_len, ncalls};
 	const CvOut pol{d_cover, d_call_start, 1, d_cover_cnt};
+	const bool pc32 = target & SYZSIG_TARGET_PC32;
 	if (flags & SYZSIG_COVER_DEDUP) {
-		SYZ_TRY((su_sort_unique<CvTile<true>, CvOut>(ctx, S, pol)));
+		// (the keys per target: header of this file)
+		if (pc32)
+			SYZ_TRY((su_sort_unique<CvTile<false>, CvOut>(ctx, S, pol)));
+		else if (target & SYZSIG_TARGET_CHECK_X86)
+			SYZ_TRY((su_sort_unique<CvTile<true>, CvOut>(ctx, S, pol)));
+		else
+			SYZ_TRY((su_sort_unique<CvTile64, CvOutLow>(ctx, S, CvOutLow{d_cover, d_call_start, 1, d_cover_cnt})));
 	} else {
-		k_cover_trunc<<<grid_cap(ncalls), kCvThreads, 0, s>>>(d_pcs, S, pol);
+		if (pc32)
+			k_cover_trunc<<<grid_cap(ncalls), kCvThreads, 0, s>>>(static_cast<const uint32_t*>(d_pcs), S, pol);
+		else
+			k_cover_trunc<<<grid_cap(ncalls), kCvThreads, 0, s>>>(static_cast<const uint64_t*>(d_pcs), S, pol);
 		SYZ_HIP(hipGetLastError());
 	}
 	SYZ_TRY(su_time_end(ctx));
@@ -183,6 +206,15 @@ extern "C" int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uin
 	if (ctx->h_cnt[kCntError])
 		return fail(SYZSIG_EIO, "edge_cover: internal: a long segment did not fit its workspace");
 	return SYZSIG_OK;
+}
+
+extern "C" int syzsig_edge_cover_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uint64_t npc,
+                                     const uint64_t* d_call_start, const uint32_t* d_call_len, uint64_t ncalls,
+                                     const uint32_t* d_prog_call, uint64_t nprog, const uint32_t* d_completed,
+                                     uint32_t flags, uint32_t* d_cover, uint32_t* d_cover_cnt)
+{
+	return syzsig_edge_cover_target_dev(ctx, d_pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog,
+	                                    d_completed, flags, SYZSIG_TARGET_LINUX_AMD64, d_cover, d_cover_cnt);
 }
 
 extern "C" int syzsig_triage_cover_dev(syzsig_ctx* ctx, uint64_t nitems, uint32_t runs, const uint8_t* d_item_flags,

@@ -219,4 +219,29 @@ struct CvTile {
 	}
 };
 
+// Full u64 PCs as keys (cover.hip, the unchecked u64 target: order and equality
+// are the u64's, only the survivors are truncated): segsort.h's plain tile of
+// one word, with the tile size and key-range alignment of the u32 tile, so that
+// k_cover_prep_calls' counts serve both (8 kCvTile bytes of LDS, 32 KB at 4096).
+struct CvTile64 : SuWordsTile<1, kCvTile> {
+	static constexpr uint32_t kAlign = kCvAlign;
+};
+static_assert(kCvTile * 8 <= 64 * 1024, "a workgroup's LDS stays at or below 64 KB");
+
+// output policy of CvTile64: executor.h:525-526, each surviving PC's low word
+// (CvOut's fields and places)
+struct CvOutLow {
+	uint32_t* out;
+	const uint64_t* out_pos;
+	uint64_t pos_stride;
+	uint32_t* out_cnt;
+	__device__ __forceinline__ uint32_t* dst(uint64_t seg) const { return out + out_pos[seg * pos_stride]; }
+	__device__ __forceinline__ uint64_t weight(uint64_t, const SuWords<1>&) const { return 1; }
+	__device__ __forceinline__ void put(uint64_t seg, uint64_t pos, const SuWords<1>& k, uint64_t) const
+	{
+		dst(seg)[pos] = (uint32_t)k.w[0];
+	}
+	__device__ __forceinline__ void finish(uint64_t seg, uint64_t total) const { out_cnt[seg] = (uint32_t)total; }
+};
+
 }  // namespace syz

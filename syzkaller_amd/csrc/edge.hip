@@ -1,6 +1,10 @@
 // edge.hip -- K1 (trace -> edge signal) + K2 (the executor's lossy dedup),
-// bit-exact with executor/executor.h:492-512 write_coverage_signal<uint64>,
-// :677-685 hash and :687-706 dedup, and executor_linux.cc:196-204 cover_check.
+// bit-exact with executor/executor.h:492-512 write_coverage_signal<cover_t>,
+// :677-685 hash and :687-706 dedup, and the executor's cover_check, for the
+// three KCOV targets of syzsig.h: <uint64> with the x86 text range
+// (executor_linux.cc:196-204 on i386 / x86_64; the one the benchmark runs),
+// <uint64> unchecked (every other executor) and <uint32> (a 32-bit kernel,
+// :595-598; cover_check(uint32) is `return true`).
 //
 // One workgroup of kEdgeWaves waves per program (= one forked executor
 // child): the 32 KB dedup table lives in LDS for the program's lifetime, calls
@@ -58,6 +62,8 @@
 // chunks ahead of the chunk being deduplicated, ping-ponging between two
 // register buffers.
 #include "internal.h"
+
+#include "edge_args.h"
 
 namespace syz {
 
@@ -123,14 +129,29 @@ __device__ __forceinline__ void lds_barrier()
 // this epoch's markers (older epochs compare lower): it was set by a position
 // before mine this epoch  <=>  stamp > my own v = epoch << kPosBits | (kPosMask - pos).
 
-template <uint32_t W, uint32_t KS, bool kMarkAll>
-__global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restrict__ pcs, uint64_t npc,
+// The KCOV target (syzsig.h SYZSIG_TARGET_*): PC = cover_t, the trace's element
+// type, and kCheckX86 = whether cover_check(cover_t) is the x86 text range or
+// `return true`.  They decide what is loaded and whether a PC can abort; from
+// `sig` on nothing depends on them (hash, dedup and write_output take uint32,
+// executor.h:677, :692, :206: sig's low word is (u32)pc ^ hash((u32)prev pc)).
+template <bool kCheckX86, typename PC>
+__device__ __forceinline__ bool edge_pc_ok(PC pc)
+{
+	if constexpr (kCheckX86)
+		return cover_check(pc);
+	else
+		return true;
+}
+
+template <uint32_t W, uint32_t KS, bool kMarkAll, typename PC = uint64_t, bool kCheckX86 = true>
+__global__ __launch_bounds__(64 * W) void k_edge_dedup(const PC* __restrict__ pcs, uint64_t npc,
                                                            const uint64_t* __restrict__ call_start,
                                                            const uint32_t* __restrict__ call_len, uint64_t ncalls,
                                                            const uint32_t* __restrict__ prog_call, uint64_t nprog,
                                                            uint32_t* sigs, uint32_t* sig_cnt, uint32_t* completed,
                                                            unsigned long long* cnt)
 {
+	static_assert(sizeof(PC) == 8 || !kCheckX86, "cover_check(uint32) is `return true`: no checked u32 target");
 	using G = EdgeGeom<W, KS>;
 	constexpr uint32_t kEdgeWaves = W, kLanes = G::kLanes, kEdgeChunk = G::kChunk, kEpochMax = G::kEpochMax;
 	constexpr uint32_t kDepth = G::kDepth;
@@ -214,6 +235,8 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 			const uint32_t len = call_len[c];
 			if (len >= kCoverSize || start > npc || len > npc - start) {
 				// executor_linux.cc:186-187 fail("too much cover") / malformed input
+				// (edge_args.h's edge_call_bad, as above edge_prog_bad, written out: through the
+				// call the compiler spills four more SGPRs in the passes kernel)
 				err += threadIdx.x == 0;
 				aborted = true;
 				done = c - cb;
@@ -230,7 +253,7 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 			// Loads are unconditional (index clamped into the call, value masked
 			// later): a load under a branch makes the compiler drain vmcnt(0)
 			// before the first use, i.e. wait for the whole prefetch.
-			auto fetch = [&](uint64_t (&buf)[kDepth][KS], uint32_t g) {
+			auto fetch = [&](PC (&buf)[kDepth][KS], uint32_t g) {
 #pragma unroll
 				for (uint32_t u = 0; u < kDepth; u++)
 #pragma unroll
@@ -238,7 +261,7 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 						buf[u][k] = pcs[min<uint64_t>(start + (uint64_t)(g + u) * kEdgeChunk + k * kLanes + pos, last)];
 			};
 			// chunk q of the call; false once the program aborts
-			auto chunk = [&](const uint64_t (&pcv)[KS], uint32_t sgv, uint32_t q) -> bool {
+			auto chunk = [&](const PC (&pcv)[KS], uint32_t sgv, uint32_t q) -> bool {
 				uint32_t sig[KS], b0[KS], b1[KS], v[KS], wpos[KS];
 				bool pending[KS], emit[KS], writer[KS], blocked[KS];
 				bool bad = false;
@@ -250,18 +273,24 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 				for (uint32_t k = 0; k < (kGroupK1 ? 0 : KS); k++) {
 					const uint32_t j = q * kEdgeChunk + k * kLanes + pos;
 					pending[k] = j < len;
-					const uint64_t pc = pending[k] ? pcv[k] : 0;
+					const PC pc = pending[k] ? pcv[k] : 0;
 					// cover_check (executor_linux.cc:196-204): doexit(0), this call and
 					// the rest of the program publish nothing
-					bad |= pending[k] && !cover_check(pc);
+					bad |= pending[k] && !edge_pc_ok<kCheckX86>(pc);
 					const uint32_t h = exec_hash((uint32_t)pc);
 					sig[k] = __shfl_up(h, 1, 64);
 					if (lane == 63)
 						s_carry[q & 1][k][w] = h;
 					b0[k] = (uint32_t)pc;  // (the PC's low half, until the previous hash is known)
 				}
-				if (!kGroupK1 && wg_any(bad, 0))
-					return false;
+				if constexpr (!kGroupK1) {  // (the barrier also publishes s_carry)
+					if constexpr (kCheckX86) {
+						if (wg_any(bad, 0))
+							return false;
+					} else {
+						lds_barrier();
+					}
+				}
 #pragma unroll
 				for (uint32_t k = 0; k < KS; k++) {
 					if constexpr (!kGroupK1) {
@@ -564,21 +593,26 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 			// K1 of a prefetch group (kGroupK1): sig_i = (u32)pc_i ^ hash((u32)pc_{i-1})
 			// for its chunks; a cover_check failure anywhere in them aborts the call
 			// before any of them runs (the call publishes nothing either way)
-			auto k1 = [&](const uint64_t (&buf)[kDepth][KS], uint32_t g, uint32_t (&sgv)[kDepth]) -> bool {
+			auto k1 = [&](const PC (&buf)[kDepth][KS], uint32_t g, uint32_t (&sgv)[kDepth]) -> bool {
 				uint32_t lo[kDepth], badm = 0;
 #pragma unroll
 				for (uint32_t u = 0; u < kDepth; u++) {
 					const bool pend = (g + u) * kEdgeChunk + pos < len;
-					const uint64_t pc = pend ? buf[u][0] : 0;
-					badm |= __ballot(pend && !cover_check(pc)) ? 1u << u : 0u;
+					const PC pc = pend ? buf[u][0] : 0;
+					if constexpr (kCheckX86)
+						badm |= __ballot(pend && !cover_check(pc)) ? 1u << u : 0u;
 					const uint32_t h = exec_hash((uint32_t)pc);
 					sgv[u] = __shfl_up(h, 1, 64);
 					if (lane == 63)
 						s_carry[u][0][w] = h;
 					lo[u] = (uint32_t)pc;
 				}
-				if (wg_any(badm != 0, 0))
-					return false;
+				if constexpr (kCheckX86) {
+					if (wg_any(badm != 0, 0))
+						return false;
+				} else {
+					lds_barrier();  // (no PC aborts: the barrier alone, for s_carry)
+				}
 #pragma unroll
 				for (uint32_t u = 0; u < kDepth; u++) {
 					if (lane == 0)
@@ -589,7 +623,7 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 				return true;
 			};
 			{
-				auto run = [&](const uint64_t (&buf)[kDepth][KS], uint32_t g) -> bool {
+				auto run = [&](const PC (&buf)[kDepth][KS], uint32_t g) -> bool {
 					uint32_t sgv[kDepth] = {};
 					if constexpr (kGroupK1) {
 						if (!k1(buf, g, sgv))
@@ -601,7 +635,7 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 							return false;
 					return true;
 				};
-				uint64_t ba[kDepth][KS], bb[kDepth][KS];
+				PC ba[kDepth][KS], bb[kDepth][KS];
 				fetch(ba, 0);
 				for (uint32_t g = 0;;) {
 					fetch(bb, g + kDepth);
@@ -645,15 +679,33 @@ __global__ __launch_bounds__(64 * W) void k_edge_dedup(const uint64_t* __restric
 
 using namespace syz;
 
-extern "C" int syzsig_edge_derive_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uint64_t npc,
-                                      const uint64_t* d_call_start, const uint32_t* d_call_len, uint64_t ncalls,
-                                      const uint32_t* d_prog_call, uint64_t nprog, uint32_t* d_sigs,
-                                      uint32_t* d_sig_cnt, uint32_t* d_completed)
+// one launch of the production geometry (4 waves) for a target's PC type and check
+template <typename PC, bool kCheckX86>
+static void edge_launch(syzsig_ctx* ctx, bool mark_all, int grid, const void* d_pcs, uint64_t npc,
+                        const uint64_t* d_call_start, const uint32_t* d_call_len, uint64_t ncalls,
+                        const uint32_t* d_prog_call, uint64_t nprog, uint32_t* d_sigs, uint32_t* d_sig_cnt,
+                        uint32_t* d_completed)
+{
+	const PC* pcs = static_cast<const PC*>(d_pcs);
+	if (mark_all)
+		k_edge_dedup<4, kEdgeKS, true, PC, kCheckX86><<<grid, 256, 0, ctx->stream>>>(
+			pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed, ctx->d_cnt);
+	else
+		k_edge_dedup<4, kEdgeKS, false, PC, kCheckX86><<<grid, 256, 0, ctx->stream>>>(
+			pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed, ctx->d_cnt);
+}
+
+extern "C" int syzsig_edge_derive_target_dev(syzsig_ctx* ctx, const void* d_pcs, uint64_t npc,
+                                             const uint64_t* d_call_start, const uint32_t* d_call_len,
+                                             uint64_t ncalls, const uint32_t* d_prog_call, uint64_t nprog,
+                                             uint32_t target, uint32_t* d_sigs, uint32_t* d_sig_cnt,
+                                             uint32_t* d_completed)
 {
 	SYZ_LOCK(ctx);
-	if (!ctx || (nprog && (!d_prog_call || !d_completed)) || (ncalls && (!d_call_start || !d_call_len || !d_sig_cnt)) ||
-	    (npc && (!d_pcs || !d_sigs)))
-		return fail(SYZSIG_EINVAL, "edge_derive: NULL argument");
+	const EdgeStatus a = edge_derive_args(ctx, d_pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog, target,
+	                                      d_sigs, d_sig_cnt, d_completed);
+	if (a.code != SYZSIG_OK)
+		return fail(a.code, a.msg);
 	if (nprog == 0)
 		return SYZSIG_OK;
 	SYZ_TRY(counters_reset(ctx));
@@ -666,30 +718,33 @@ extern "C" int syzsig_edge_derive_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, ui
 	const bool mark_all = ctx->agg_dbg & SYZSIG_DEBUG_EDGE_MARKALL   ? true
 	                      : ctx->agg_dbg & SYZSIG_DEBUG_EDGE_PASSES ? false
 	                                                                : ctx->edge_mark_all;
+	if (target & SYZSIG_TARGET_PC32) {
+		edge_launch<uint32_t, false>(ctx, mark_all, grid, d_pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog,
+		                             d_sigs, d_sig_cnt, d_completed);
+	} else if (!(target & SYZSIG_TARGET_CHECK_X86)) {
+		edge_launch<uint64_t, false>(ctx, mark_all, grid, d_pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog,
+		                             d_sigs, d_sig_cnt, d_completed);
+	} else {
 #ifdef SYZ_EXPERIMENTS
-	// measured slower: 8 waves 25 ms, 2 waves 16.1, 1 wave 21.3 vs 4 waves 14.9 at C2
-	if (ctx->edge_waves == 8)
-		k_edge_dedup<8, kEdgeKS, false><<<grid, 512, 0, ctx->stream>>>(d_pcs, npc, d_call_start, d_call_len, ncalls,
-		                                                          d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
-		                                                          ctx->d_cnt);
-	else if (ctx->edge_waves == 2)
-		k_edge_dedup<2, kEdgeKS, false><<<grid, 128, 0, ctx->stream>>>(d_pcs, npc, d_call_start, d_call_len, ncalls,
-		                                                          d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
-		                                                          ctx->d_cnt);
-	else if (ctx->edge_waves == 1)
-		k_edge_dedup<1, kEdgeKS, false><<<grid, 64, 0, ctx->stream>>>(d_pcs, npc, d_call_start, d_call_len, ncalls,
-		                                                         d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
-		                                                         ctx->d_cnt);
-	else
+		// measured slower: 8 waves 25 ms, 2 waves 16.1, 1 wave 21.3 vs 4 waves 14.9 at C2
+		const uint64_t* pcs = static_cast<const uint64_t*>(d_pcs);
+		if (ctx->edge_waves == 8)
+			k_edge_dedup<8, kEdgeKS, false><<<grid, 512, 0, ctx->stream>>>(pcs, npc, d_call_start, d_call_len, ncalls,
+			                                                          d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
+			                                                          ctx->d_cnt);
+		else if (ctx->edge_waves == 2)
+			k_edge_dedup<2, kEdgeKS, false><<<grid, 128, 0, ctx->stream>>>(pcs, npc, d_call_start, d_call_len, ncalls,
+			                                                          d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
+			                                                          ctx->d_cnt);
+		else if (ctx->edge_waves == 1)
+			k_edge_dedup<1, kEdgeKS, false><<<grid, 64, 0, ctx->stream>>>(pcs, npc, d_call_start, d_call_len, ncalls,
+			                                                         d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
+			                                                         ctx->d_cnt);
+		else
 #endif
-	if (mark_all)
-		k_edge_dedup<4, kEdgeKS, true><<<grid, 256, 0, ctx->stream>>>(d_pcs, npc, d_call_start, d_call_len, ncalls,
-		                                                         d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
-		                                                         ctx->d_cnt);
-	else
-		k_edge_dedup<4, kEdgeKS, false><<<grid, 256, 0, ctx->stream>>>(d_pcs, npc, d_call_start, d_call_len, ncalls,
-		                                                          d_prog_call, nprog, d_sigs, d_sig_cnt, d_completed,
-		                                                          ctx->d_cnt);
+			edge_launch<uint64_t, true>(ctx, mark_all, grid, d_pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call,
+			                            nprog, d_sigs, d_sig_cnt, d_completed);
+	}
 	SYZ_HIP(hipGetLastError());
 	if (ctx->timing)
 		SYZ_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
@@ -704,4 +759,13 @@ extern "C" int syzsig_edge_derive_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, ui
 	if (npc)
 		ctx->edge_mark_all = ctx->h_cnt[kCntAux] * 100 < (unsigned long long)kEdgeMarkAllMaxDupPct * npc;
 	return SYZSIG_OK;
+}
+
+extern "C" int syzsig_edge_derive_dev(syzsig_ctx* ctx, const uint64_t* d_pcs, uint64_t npc,
+                                      const uint64_t* d_call_start, const uint32_t* d_call_len, uint64_t ncalls,
+                                      const uint32_t* d_prog_call, uint64_t nprog, uint32_t* d_sigs,
+                                      uint32_t* d_sig_cnt, uint32_t* d_completed)
+{
+	return syzsig_edge_derive_target_dev(ctx, d_pcs, npc, d_call_start, d_call_len, ncalls, d_prog_call, nprog,
+	                                     SYZSIG_TARGET_LINUX_AMD64, d_sigs, d_sig_cnt, d_completed);
 }

@@ -115,9 +115,22 @@ class Device:
         return st.as_dict()
 
     # ---------------------------------------------------------------- K1+K2
-    def edge_derive(self, pcs, call_start, call_len, prog_call, sigs=None, sig_cnt=None, completed=None):
-        """executor write_coverage_signal for every program of a batch."""
+    def _trace_target(self, pcs, target, who):
+        """The target word of a trace call and the dtype check that goes with it
+        (None: the entry point without a target, int64 PCs under the x86 check)."""
+        t = _lib.SYZSIG_TARGET_LINUX_AMD64 if target is None else int(target)
+        want = {0: torch.int64, _lib.SYZSIG_TARGET_CHECK_X86: torch.int64, _lib.SYZSIG_TARGET_PC32: torch.int32}.get(t)
+        # (any other target word: the library rejects it; no target: today's call, unchecked as ever)
+        if target is not None and want is not None and pcs.dtype != want:
+            raise ValueError(f"{who}: pcs is {pcs.dtype}, target {t} takes {want}")
+        return t
+
+    def edge_derive(self, pcs, call_start, call_len, prog_call, sigs=None, sig_cnt=None, completed=None, target=None):
+        """executor write_coverage_signal for every program of a batch.  target
+        (syzkaller_amd.targets; None = linux/amd64, today's call): pcs is int32
+        for a PC32 target and int64 otherwise."""
         self._check_dev(pcs, call_start, call_len, prog_call, sigs, sig_cnt, completed)
+        t = self._trace_target(pcs, target, "edge_derive")
         nprog = prog_call.numel() - 1
         if sigs is None:
             sigs = torch.empty(pcs.numel(), dtype=torch.int32, device=self.dev)
@@ -125,25 +138,41 @@ class Device:
             sig_cnt = torch.empty(call_len.numel(), dtype=torch.int32, device=self.dev)
         if completed is None:
             completed = torch.empty(max(nprog, 0), dtype=torch.int32, device=self.dev)
-        check(self.L.syzsig_edge_derive_dev(self.eng.h, _p(pcs), pcs.numel(), _p(call_start), _p(call_len),
-                                            call_len.numel(), _p(prog_call), max(nprog, 0), _p(sigs), _p(sig_cnt),
-                                            _p(completed)))
+        if target is None:
+            check(self.L.syzsig_edge_derive_dev(self.eng.h, _p(pcs), pcs.numel(), _p(call_start), _p(call_len),
+                                                call_len.numel(), _p(prog_call), max(nprog, 0), _p(sigs), _p(sig_cnt),
+                                                _p(completed)))
+        else:
+            check(self.L.syzsig_edge_derive_target_dev(self.eng.h, _p(pcs), pcs.numel(), _p(call_start), _p(call_len),
+                                                       call_len.numel(), _p(prog_call), max(nprog, 0), t, _p(sigs),
+                                                       _p(sig_cnt), _p(completed)))
         return sigs, sig_cnt, completed
 
-    def edge_cover(self, pcs, call_start, call_len, prog_call, completed, dedup=True, cover=None, cover_cnt=None):
+    def edge_cover(self, pcs, call_start, call_len, prog_call, completed, dedup=True, cover=None, cover_cnt=None,
+                   target=None):
         """executor.h:514-527 for every call of a batch (syzsig_edge_cover_dev):
         the cover output of the traces edge_derive took, `completed` as it
-        returned it.  dedup = flag_dedup_cover.  Returns (cover int32[npc], call
-        c's at cover[call_start[c] : +cover_cnt[c]], cover_cnt int32[ncalls])."""
+        returned it.  dedup = flag_dedup_cover.  target as in edge_derive: with
+        dedup, target 0 sorts and uniques the u64 PCs before truncating, so its
+        output follows the u64 order and may repeat a low word.  Returns (cover
+        int32[npc], call c's at cover[call_start[c] : +cover_cnt[c]], cover_cnt
+        int32[ncalls])."""
         self._check_dev(pcs, call_start, call_len, prog_call, completed, cover, cover_cnt)
+        t = self._trace_target(pcs, target, "edge_cover")
         nprog = prog_call.numel() - 1
         if cover is None:
             cover = torch.empty(pcs.numel(), dtype=torch.int32, device=self.dev)
         if cover_cnt is None:
             cover_cnt = torch.empty(call_len.numel(), dtype=torch.int32, device=self.dev)
-        check(self.L.syzsig_edge_cover_dev(self.eng.h, _p(pcs), pcs.numel(), _p(call_start), _p(call_len),
-                                           call_len.numel(), _p(prog_call), max(nprog, 0), _p(completed),
-                                           _lib.SYZSIG_COVER_DEDUP if dedup else 0, _p(cover), _p(cover_cnt)))
+        flags = _lib.SYZSIG_COVER_DEDUP if dedup else 0
+        if target is None:
+            check(self.L.syzsig_edge_cover_dev(self.eng.h, _p(pcs), pcs.numel(), _p(call_start), _p(call_len),
+                                               call_len.numel(), _p(prog_call), max(nprog, 0), _p(completed), flags,
+                                               _p(cover), _p(cover_cnt)))
+        else:
+            check(self.L.syzsig_edge_cover_target_dev(self.eng.h, _p(pcs), pcs.numel(), _p(call_start), _p(call_len),
+                                                      call_len.numel(), _p(prog_call), max(nprog, 0), _p(completed),
+                                                      flags, t, _p(cover), _p(cover_cnt)))
         return cover, cover_cnt
 
     # ---------------------------------------------------------------- comparison hints
