@@ -65,8 +65,8 @@ int syzsig_ctx_set_timing(syzsig_ctx* ctx, int enable);
  * syzsig_triage_cover_dev, syzsig_triage_items_dev, syzsig_exec_comps_dev,
  * syzsig_comp_map_dev, syzsig_shrink_expand_dev, syzsig_hint_mutants_dev, syzsig_hash_dev or
  * syzsig_sigset_add_dev call, or of the last syzsig_calc_prios_dev, syzsig_static_prio_finish_dev,
- * syzsig_choice_table_dev, syzsig_choice_lookup_dev, syzsig_call_cover_dev, syzsig_report_pcs_dev or
- * syzsig_uncovered_pcs_dev call (uploads / first kernel to its last kernel,
+ * syzsig_choice_table_dev, syzsig_choice_lookup_dev, syzsig_call_cover_dev, syzsig_report_pcs_dev,
+ * syzsig_uncovered_pcs_dev or syzsig_file_set_dev call (uploads / first kernel to its last kernel,
  * including the host round trips between); for syzsig_manager_new_input_batch
  * the host wall time of the call, which ends synchronised. */
 double syzsig_ctx_last_ms(syzsig_ctx* ctx);
@@ -944,6 +944,42 @@ int syzsig_uncovered_pcs_dev(syzsig_ctx* ctx, const uint64_t* d_sym_start, const
  * included), out[1] = the rank-merge passes over them, out[2] = functions
  * handled, out[3] = those whose site range was walked by a workgroup. */
 int syzsig_report_stats(syzsig_ctx* ctx, uint64_t out[4]);
+/* fileSet (cover.go:162-193) and the per-file Coverage count of
+ * generateCoverHTML's line walk (cover.go:129-148) over symbolized frames.  The
+ * caller interns Frame.File and Frame.Func to dense ids (file < nfiles, func <
+ * nfuncs; funcs is keyed by the function's name alone, so one name is one id
+ * whatever its file) and passes each list as three parallel arrays; lines are
+ * Frame.Line as int32, the whole range, ordered as signed.  The order of frames
+ * within a list does not matter; the covered list is applied first, as in Go:
+ * an uncovered frame counts only if its function has a covered frame, and a
+ * line that is covered stays covered.
+ * Outputs, as CSR over the files: file f's sorted list is d_line / d_covered
+ * [d_off[f] .. d_off[f + 1]) (nfiles + 1 offsets from 0), lines strictly
+ * ascending, covered 0 or 1.  A file without entries has an empty range (the
+ * Go map has no such key).  cap = room in d_line and d_covered; a cap below the
+ * entries of all lists is SYZSIG_ERANGE (ncov + nunc always suffices), a file
+ * or function id out of range SYZSIG_EINVAL, both checked before anything is
+ * written.
+ * d_nlines (nfiles; NULL: the lists only, and then d_shown and d_coverage are
+ * NULL too, else neither is): len(parseFile(f)) per file.  d_shown[f] = the
+ * entries the walk consumes: 0 when the list is empty or its first line is
+ * below 1 (an entry that is never consumed blocks all behind it: `?:0` of
+ * addr2line), else the entries with line <= nlines; d_coverage[f] = the
+ * covered ones among the first d_shown[f] = templateFile.Coverage.
+ * SYZSIG_FILESET_TILE: a file with at most this many frames (covered plus
+ * kept uncovered, repeats included) is sorted in LDS by one workgroup.
+ * ncov + nunc < 2^31; nfiles, nfuncs < 2^32. */
+#define SYZSIG_FILESET_TILE 2048
+int syzsig_file_set_dev(syzsig_ctx* ctx, const uint32_t* d_cov_file, const int32_t* d_cov_line,
+                        const uint32_t* d_cov_func, uint64_t ncov, const uint32_t* d_unc_file,
+                        const int32_t* d_unc_line, const uint32_t* d_unc_func, uint64_t nunc, uint64_t nfiles,
+                        uint64_t nfuncs, const uint32_t* d_nlines, uint64_t* d_off, int32_t* d_line,
+                        uint8_t* d_covered, uint64_t cap, uint32_t* d_shown, uint32_t* d_coverage);
+/* The paths of the context's last syzsig_file_set_dev call: out[0] = uncovered
+ * frames kept (their function has a covered frame), out[1] = files of more
+ * than SYZSIG_FILESET_TILE frames, out[2] = the rank-merge passes over them,
+ * out[3] = entries written. */
+int syzsig_file_set_stats(syzsig_ctx* ctx, uint64_t out[4]);
 
 /* ---- hash-sharded maxSignal across GPUs (one process per GPU) ----
  * The batch is split by program range over G GPUs (serial order = GPU-major);

@@ -7,6 +7,8 @@ include/syzsig.h).  This package is its Python host side:
              minimize, shard routing)
   dist    -- hash-sharded maxSignal over one process per GPU
   targets -- the KCOV target of a kernel under test (PC width, cover_check)
+  report  -- the coverage pages' corpus-wide loops (per-call cover, report PCs,
+             uncovered PCs, fileSet and the per-file Coverage)
   synth   -- host-side synthetic KCOV workload (same generator as on device)
 """
 from ._lib import LIB_PATH, SyzsigError, CorruptedSerial  # noqa: F401

@@ -47,6 +47,7 @@ SYZSIG_HASH_LONG = 4096  # ... a message past this goes to the second launch
 SYZSIG_SIGSET_TILE = 2048  # the sort tile of a batch of Sigs (sigs.hip)
 SYZSIG_PRIO_MAX_CALLS = 16384  # syzsig_calc_prios_dev: len(target.Syscalls) at most (one LDS row, prio.hip)
 SYZSIG_PRIO_SPLIT = 4096  # ... a call with more occurrences has its row counted in slices
+SYZSIG_FILESET_TILE = 2048  # syzsig_file_set_dev: a file of more frames leaves the one-workgroup LDS sort (report.hip)
 SYZSIG_ARCH_AMD64, SYZSIG_ARCH_386, SYZSIG_ARCH_ARM64, SYZSIG_ARCH_ARM, SYZSIG_ARCH_PPC64LE = range(5)  # report_pcs
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
@@ -198,6 +199,9 @@ SIGNATURES = {
     "syzsig_report_pcs_dev": (c_int, [_P, _P, c_uint64, c_uint32, c_uint32, _P, _P]),
     "syzsig_uncovered_pcs_dev": (c_int, [_P, _P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, POINTER(c_uint64)]),
     "syzsig_report_stats": (c_int, [_P, _P]),
+    "syzsig_file_set_dev": (c_int, [_P, _P, _P, _P, c_uint64, _P, _P, _P, c_uint64, c_uint64, c_uint64, _P, _P, _P, _P,
+                                    c_uint64, _P, _P]),
+    "syzsig_file_set_stats": (c_int, [_P, _P]),
     "syzsig_ingest_exec_output_dev": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P, _P, _P, _P,
                                               _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_triage_records_dev": (c_int, [_P, _P, _PP, _P, c_uint64, _P, c_uint32, _P,

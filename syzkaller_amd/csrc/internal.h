@@ -205,6 +205,7 @@ enum WsSlot : int {
 	kWsPqPart = 74,
 	// report.hip: a call's counts, offsets and cursors; the PCs in call order | the keys of report_pcs;
 	// the sorted survivors before the gather | uncovered_pcs' add / del words and block counts
+	// | file_set's per-file counts, offsets and the funcs bitmap; the keys in file order; the sorted lists
 	kWsRcMeta = 75,
 	kWsRcStage = 76,
 	kWsRcStage2 = 77,
@@ -274,6 +275,7 @@ struct syzsig_ctx {
 	uint64_t hs_stats[4] = {0, 0, 0, 0};  // syzsig_hash_stats: the last hash call's paths (sigs.hip)
 	uint64_t pq_stats[4] = {0, 0, 0, 0};  // syzsig_prio_stats: the last calc_prios call's paths (prio.hip)
 	uint64_t rc_stats[4] = {0, 0, 0, 0};  // syzsig_report_stats: the last coverage-report call's paths (report.hip)
+	uint64_t fs_stats[4] = {0, 0, 0, 0};  // syzsig_file_set_stats: the last file_set call's paths (report.hip)
 	bool hash_stage = true;              // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
 };
 

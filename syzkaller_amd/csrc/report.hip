@@ -51,6 +51,30 @@
 // A function's range is walked by the wave that owns its slot, or, past
 // kReportWaveSites sites, by a workgroup (k_un_add_block) from a list.
 //   k_un_count / k_su_scan / k_un_write   the survivors compacted in order.
+//
+// syzsig_file_set_dev: fileSet (cover.go:162-193) and the line walk's Coverage
+// count (cover.go:129-148) over frames whose File and Func are dense ids.
+//   k_fs_pass<covered>      funcs[Func] = true as one bit per function id, the
+//                           ids checked, per file the frames (histogram)
+//   k_fs_pass<uncovered>    the same for the frames whose function has its bit
+//                           (a separate launch: every covered frame came first)
+//   k_rc_seglens, k_su_scan segsort.h's plan; the files' ranges
+//   k_fs_pass<.., scatter>  every counted frame's key to its file's range.  Frames
+//                           of neighbouring PCs share a file: one atomic per run
+//                           of equal neighbours in a wave (fs_run_add)
+//   su_sort_unique          over nfiles segments with the plain one-word tile.
+//                           Key = file_set_key: the line in signed order, then
+//                           covered before uncovered.  The key type calls two
+//                           keys equal when their lines are: what survives the
+//                           sort-unique is each line's first key -- its covered
+//                           entry if it has one -- so `true` is never overwritten
+//                           and a line is listed once, without a pass of its own
+//   k_su_scan               the lists' lengths -> the CSR offsets, the total
+//                           (cap is checked against it; nothing is written before)
+//   k_fs_emit / _block      per file, by a wave or (past kFileSetWaveEntries) a
+//                           workgroup from a list: keys -> (line, covered), and
+//                           the walk in closed form -- the head's sign, an upper
+//                           bound of nlines, a sum over the flags before it.
 #include <algorithm>
 
 #include "cover_tile.h"
@@ -341,6 +365,199 @@ __global__ __launch_bounds__(kRcThreads) void k_un_write(const uint64_t* __restr
 	}
 }
 
+// ---- fileSet and the line walk ----
+
+constexpr uint32_t kFsTile = SYZSIG_FILESET_TILE;
+constexpr int kFsBadFile = kCntError, kFsBadFunc = kCntInserted, kFsKept = kSuTotal, kFsLong = kCntSpill;
+
+// file_set_key as a sort key: ordered as the word it is, equal when the lines are
+struct FsKey : SuU64<1> {
+	static __device__ __forceinline__ bool eq(const T& a, const T& b) { return (a.w[0] >> 1) == (b.w[0] >> 1); }
+};
+
+// the plain one-word tile, its survivors chosen by FsKey::eq
+struct FsTile : SuWordsTile<1, kFsTile> {
+	using Key = FsKey;
+	template <typename Pol>
+	static __device__ __forceinline__ uint64_t unique_lds(uint32_t n, uint64_t seg, const Pol& pol, const Lds& t)
+	{
+		return su_unique_write<Key>(n, seg, pol, [&](uint32_t i) { return t.get(i); });
+	}
+	template <typename Pol>
+	static __device__ __forceinline__ uint64_t unique_buf(uint32_t n, uint64_t seg, const Pol& pol, const uint64_t* s)
+	{
+		return su_unique_write<Key>(n, seg, pol, [&](uint32_t i) { return Key::get(s, i); });
+	}
+};
+
+struct FsFrames {
+	const uint32_t* file;
+	const int32_t* line;
+	const uint32_t* func;
+	uint64_t n;
+};
+
+// ctr[id] += 1 for every lane that is `on`, with one atomic per run of
+// neighbouring lanes that are on and hold the same id; returns this lane's
+// place: the count before its run plus its rank in the run.  The whole wave
+// calls it.
+__device__ __forceinline__ uint32_t fs_run_add(uint32_t* ctr, uint32_t id, bool on)
+{
+	const uint32_t lane = lane_id();
+	const uint32_t key = on ? id : 0xffffffffu;  // (an id that is on is below 2^32 - 1)
+	const uint32_t prev = __shfl_up(key, 1, 64);
+	const bool head = on && (lane == 0 || prev != key);
+	const uint64_t heads = __ballot(head), stops = heads | ~__ballot(on);
+	// an on lane has a head at or below it: lane 0, or the first on lane after an off one
+	const uint32_t hl = on ? 63 - (uint32_t)__clzll((long long)(heads & (~0ull >> (63 - lane)))) : lane;
+	const uint64_t after = hl == 63 ? 0 : stops & (~0ull << (hl + 1));
+	const uint32_t end = after ? (uint32_t)__ffsll((long long)after) - 1 : 64;
+	uint32_t at = 0;
+	if (head)
+		at = atomicAdd(&ctr[id], end - lane);
+	at = __shfl(at, hl, 64);
+	return at + (lane - hl);
+}
+
+// One pass over one list of frames.  kCovered: cover.go:165-171, funcs[Func] =
+// true as a bit; else cover.go:172-175, a frame whose function has no bit is
+// skipped.  !kScatter: the ids checked, per_file = the files' histogram, the
+// kept frames counted.  kScatter: per_file = the files' cursors (from 0), every
+// frame the histogram counted puts its key into its file's range of `stage`.
+template <bool kCovered, bool kScatter>
+__global__ __launch_bounds__(kRcThreads) void k_fs_pass(FsFrames F, uint32_t nfiles, uint32_t nfuncs, uint32_t* funcs,
+                                                        uint32_t* per_file, const uint64_t* __restrict__ seg_off,
+                                                        uint64_t cap, uint64_t* stage, unsigned long long* cnt)
+{
+	const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
+	uint64_t bad_file = 0, bad_func = 0, kept = 0;
+	for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < F.n; i0 += T) {  // (uniform per workgroup)
+		const uint64_t i = i0 + threadIdx.x;
+		uint32_t file = 0, func = 0;
+		bool on = false;
+		if (i < F.n) {
+			file = F.file[i];
+			func = F.func[i];
+			bad_file += file >= nfiles;
+			bad_func += func >= nfuncs;
+			on = file < nfiles && func < nfuncs;
+		}
+		if (on && !(kCovered && kScatter)) {
+			// neighbouring frames share a function: most lanes find the bit set and issue no atomic
+			const uint32_t bit = 1u << (func & 31), have = __atomic_load_n(&funcs[func >> 5], __ATOMIC_RELAXED) & bit;
+			if (!kCovered)
+				on = have != 0;
+			else if (!kScatter && !have)
+				atomicOr(&funcs[func >> 5], bit);
+		}
+		kept += on;
+		const uint32_t at = fs_run_add(per_file, file, on);
+		if (kScatter && on) {
+			const uint64_t p = seg_off[file] + at;
+			if (p < cap)  // (the ranges are the histogram's: cannot fail)
+				stage[p] = file_set_key(F.line[i], kCovered);
+		}
+	}
+	if (!kScatter) {
+		block_count(&cnt[kFsBadFile], bad_file);
+		block_count(&cnt[kFsBadFunc], bad_func);
+		if (!kCovered)
+			block_count(&cnt[kFsKept], kept);
+	}
+}
+
+// A file's sorted keys src[0 .. n) to entries dst .. of the outputs; this
+// thread takes first, first + stride, ...  With `walk`, shown = the entries the
+// walk of cover.go:131-143 consumes, and the return value is this thread's
+// share of the covered ones among them.
+__device__ __forceinline__ uint32_t fs_emit_file(const uint64_t* __restrict__ src, uint32_t n, uint64_t dst, bool walk,
+                                                 uint32_t nlines, uint32_t first, uint32_t stride, int32_t* line,
+                                                 uint8_t* covered, uint32_t& shown)
+{
+	shown = 0;
+	if (walk && n && file_set_key_line(src[0]) >= 1)  // a head below line 1 is never consumed and blocks the rest
+		shown = su_search<uint32_t>(
+			0, n, [&](uint32_t mid) { return file_set_line_within(file_set_key_line(src[mid]), nlines); });
+	uint32_t c = 0;
+	for (uint32_t i = first; i < n; i += stride) {
+		const uint64_t k = src[i];
+		const bool cv = file_set_key_covered(k);
+		line[dst + i] = file_set_key_line(k);
+		covered[dst + i] = cv;
+		c += cv && i < shown;
+	}
+	return c;
+}
+
+// one wave per file; the long ones listed for k_fs_emit_block
+__global__ __launch_bounds__(kRcThreads) void k_fs_emit(const uint64_t* __restrict__ stage,
+                                                        const uint64_t* __restrict__ seg_off,
+                                                        const uint32_t* __restrict__ len,
+                                                        const uint64_t* __restrict__ off, uint64_t nfiles,
+                                                        const uint32_t* __restrict__ nlines, uint64_t* d_off,
+                                                        int32_t* d_line, uint8_t* d_covered, uint32_t* d_shown,
+                                                        uint32_t* d_coverage, uint32_t* longs, unsigned long long* cnt)
+{
+	const uint64_t W = (uint64_t)gridDim.x * (kRcThreads / 64);
+	const uint32_t lane = lane_id();
+	for (uint64_t f = (uint64_t)blockIdx.x * (kRcThreads / 64) + (threadIdx.x >> 6); f < nfiles; f += W) {
+		const uint32_t n = len[f];
+		if (lane == 0)
+			d_off[f] = off[f];
+		if (file_set_block_path(n)) {
+			if (lane == 0) {
+				const uint64_t k = atomicAdd(&cnt[kFsLong], 1ull);
+				if (k < nfiles)
+					longs[k] = (uint32_t)f;
+			}
+			continue;
+		}
+		uint32_t shown;
+		const uint32_t c = (uint32_t)wave_sum_u64(fs_emit_file(stage + seg_off[f], n, off[f], nlines != nullptr,
+		                                                       nlines ? nlines[f] : 0, lane, 64, d_line, d_covered, shown));
+		if (nlines && lane == 0) {
+			d_shown[f] = shown;
+			d_coverage[f] = c;
+		}
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+		d_off[nfiles] = off[nfiles];
+}
+
+// one workgroup per listed file
+__global__ __launch_bounds__(kRcThreads) void k_fs_emit_block(const uint64_t* __restrict__ stage,
+                                                              const uint64_t* __restrict__ seg_off,
+                                                              const uint32_t* __restrict__ len,
+                                                              const uint64_t* __restrict__ off, uint64_t nfiles,
+                                                              const uint32_t* __restrict__ nlines, int32_t* d_line,
+                                                              uint8_t* d_covered, uint32_t* d_shown, uint32_t* d_coverage,
+                                                              const uint32_t* __restrict__ longs,
+                                                              const unsigned long long* cnt)
+{
+	__shared__ uint32_t s_c[kRcThreads / 64];
+	const uint64_t nl = std::min<uint64_t>(cnt[kFsLong], nfiles);
+	for (uint64_t k = blockIdx.x; k < nl; k += gridDim.x) {
+		const uint64_t f = longs[k];
+		if (f >= nfiles)
+			continue;  // (an index k_fs_emit wrote: cannot happen)
+		uint32_t shown;
+		const uint32_t c = (uint32_t)wave_sum_u64(fs_emit_file(stage + seg_off[f], len[f], off[f], nlines != nullptr,
+		                                                       nlines ? nlines[f] : 0, threadIdx.x, kRcThreads, d_line,
+		                                                       d_covered, shown));
+		if (lane_id() == 0)
+			s_c[threadIdx.x >> 6] = c;
+		__syncthreads();
+		if (nlines && threadIdx.x == 0) {
+			uint32_t sum = 0;
+			for (uint32_t x = 0; x < kRcThreads / 64; x++)
+				sum += s_c[x];
+			d_shown[f] = shown;
+			d_coverage[f] = sum;
+		}
+		__syncthreads();  // s_c is rewritten for the next file
+	}
+}
+
 static int report_fail(const ReportStatus& a) { return fail(a.code, a.msg); }
 
 #define SYZ_RARGS(expr)                                                            \
@@ -526,4 +743,85 @@ extern "C" int syzsig_uncovered_pcs_dev(syzsig_ctx* ctx, const uint64_t* d_sym_s
 extern "C" int syzsig_report_stats(syzsig_ctx* ctx, uint64_t out[4])
 {
 	return stats_copy(ctx, &syzsig_ctx::rc_stats, out, "report_stats");
+}
+
+extern "C" int syzsig_file_set_dev(syzsig_ctx* ctx, const uint32_t* d_cov_file, const int32_t* d_cov_line,
+                                   const uint32_t* d_cov_func, uint64_t ncov, const uint32_t* d_unc_file,
+                                   const int32_t* d_unc_line, const uint32_t* d_unc_func, uint64_t nunc, uint64_t nfiles,
+                                   uint64_t nfuncs, const uint32_t* d_nlines, uint64_t* d_off, int32_t* d_line,
+                                   uint8_t* d_covered, uint64_t cap, uint32_t* d_shown, uint32_t* d_coverage)
+{
+	SYZ_LOCK(ctx);
+	SYZ_RARGS(file_set_args(ctx, d_cov_file, d_cov_line, d_cov_func, ncov, d_unc_file, d_unc_line, d_unc_func, nunc, nfiles,
+	                        nfuncs, d_nlines, d_off, d_line, d_covered, cap, d_shown, d_coverage));
+	std::fill(ctx->fs_stats, ctx->fs_stats + 4, 0);
+	const hipStream_t s = ctx->stream;
+	const uint32_t nf = (uint32_t)nfiles, nfn = (uint32_t)nfuncs;
+	// hist, cur [nfiles], the funcs bitmap (zeroed); cnt, longs [nfiles]; seg_off, off [nfiles + 1]
+	char* m;
+	const size_t a32 = align256(nfiles * 4), abm = align256((nfuncs + 31) / 32 * 4), a64 = align256((nfiles + 1) * 8);
+	SYZ_TRY(ws_get(ctx, kWsRcMeta, 4 * a32 + abm + 2 * a64, (void**)&m));
+	uint32_t *hist = (uint32_t*)m, *cur = (uint32_t*)(m + a32), *funcs = (uint32_t*)(m + 2 * a32),
+	         *cnt = (uint32_t*)(m + 2 * a32 + abm), *longs = (uint32_t*)(m + 3 * a32 + abm);
+	uint64_t *seg_off = (uint64_t*)(m + 4 * a32 + abm), *off = (uint64_t*)(m + 4 * a32 + abm + a64);
+	const FsFrames C{d_cov_file, d_cov_line, d_cov_func, ncov}, U{d_unc_file, d_unc_line, d_unc_func, nunc};
+	SYZ_TRY(counters_reset(ctx));
+	SYZ_TRY(su_time_begin(ctx));
+	if (2 * a32 + abm)
+		SYZ_HIP(hipMemsetAsync(m, 0, 2 * a32 + abm, s));
+	if (ncov)
+		k_fs_pass<true, false><<<grid_for(ncov, kRcThreads), kRcThreads, 0, s>>>(C, nf, nfn, funcs, hist, nullptr, 0,
+		                                                                        nullptr, ctx->d_cnt);
+	if (nunc)
+		k_fs_pass<false, false><<<grid_for(nunc, kRcThreads), kRcThreads, 0, s>>>(U, nf, nfn, funcs, hist, nullptr, 0,
+		                                                                         nullptr, ctx->d_cnt);
+	k_rc_seglens<FsTile::kTile, FsTile::kAlign><<<grid_for(nfiles, kRcThreads), kRcThreads, 0, s>>>(hist, nfiles,
+	                                                                                               ctx->d_cnt);
+	k_su_scan<<<1, kSuThreads, 0, s>>>(hist, nfiles, seg_off);
+	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(counters_fetch(ctx));
+	const unsigned long long* h = ctx->h_cnt;
+	SYZ_RARGS(file_set_frames_status(h[kFsBadFile], h[kFsBadFunc]));
+	const uint64_t kept = h[kFsKept], nlarge = h[kSuLarge], maxlen = h[kSuMaxLen], nkeys = ncov + kept;
+	uint64_t *stage, *stage2;
+	SYZ_TRY(ws_get(ctx, kWsRcStage, nkeys * 8 + 256, (void**)&stage));
+	SYZ_TRY(ws_get(ctx, kWsRcStage2, nkeys * 8 + 256, (void**)&stage2));
+	if (ncov)
+		k_fs_pass<true, true><<<grid_for(ncov, kRcThreads), kRcThreads, 0, s>>>(C, nf, nfn, funcs, cur, seg_off, nkeys,
+		                                                                       stage, ctx->d_cnt);
+	if (kept)
+		k_fs_pass<false, true><<<grid_for(nunc, kRcThreads), kRcThreads, 0, s>>>(U, nf, nfn, funcs, cur, seg_off, nkeys,
+		                                                                        stage, ctx->d_cnt);
+	if (nfiles) {
+		const SuSegs S{stage, 1, seg_off, hist, 1, hist, nfiles};
+		const SuOutKeys<FsKey> pol{stage2, seg_off, 1, cnt};
+		SYZ_TRY((su_sort_unique<FsTile, SuOutKeys<FsKey>>(ctx, S, pol)));
+	}
+	k_su_scan<<<1, kSuThreads, 0, s>>>(cnt, nfiles, off);
+	SYZ_HIP(hipGetLastError());
+	uint64_t total = 0;
+	SYZ_HIP(hipMemcpyAsync(&total, off + nfiles, 8, hipMemcpyDeviceToHost, s));
+	SYZ_TRY(counters_fetch(ctx));
+	if (ctx->h_cnt[kCntError])
+		return fail(SYZSIG_EIO, "file_set: internal: a long file did not fit its workspace");
+	SYZ_RARGS(file_set_cap_status(total, cap));
+	// nothing can fail from here on but the device itself: the outputs are written
+	k_fs_emit<<<grid_for(nfiles, kRcThreads / 64, 1 << 16), kRcThreads, 0, s>>>(
+		stage2, seg_off, cnt, off, nfiles, d_nlines, d_off, d_line, d_covered, d_shown, d_coverage, longs, ctx->d_cnt);
+	if (file_set_block_path(total))
+		k_fs_emit_block<<<grid_for(total / (kFileSetWaveEntries + 1), 1, 1024), kRcThreads, 0, s>>>(
+			stage2, seg_off, cnt, off, nfiles, d_nlines, d_line, d_covered, d_shown, d_coverage, longs, ctx->d_cnt);
+	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(su_time_end(ctx));
+	SYZ_HIP(hipStreamSynchronize(s));
+	ctx->fs_stats[0] = kept;
+	ctx->fs_stats[1] = nlarge;
+	ctx->fs_stats[2] = report_merge_passes(maxlen, kFsTile);
+	ctx->fs_stats[3] = total;
+	return SYZSIG_OK;
+}
+
+extern "C" int syzsig_file_set_stats(syzsig_ctx* ctx, uint64_t out[4])
+{
+	return stats_copy(ctx, &syzsig_ctx::fs_stats, out, "file_set_stats");
 }

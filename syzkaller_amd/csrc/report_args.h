@@ -1,8 +1,9 @@
 // report_args.h -- the host-side argument checks of report.hip's entry points:
 // what is rejected before any device work, how the counters of the device-side
-// checks become a status, and previousInstructionPC's subtrahend per arch.  No
-// HIP here, so that tests/report_driver.cc runs every branch on the CPU under
-// ASan + UBSan.  Whoever includes this has syzsig.h's codes and limits.
+// checks become a status, previousInstructionPC's subtrahend per arch, and
+// fileSet's sort key.  No HIP here, so that tests/report_driver.cc and
+// tests/fileset_driver.cc run every branch on the CPU under ASan + UBSan.
+// Whoever includes this has syzsig.h's codes and limits.
 #pragma once
 
 #include <cstdint>
@@ -126,6 +127,67 @@ inline ReportStatus uncovered_tables_status(uint64_t bad_cover, uint64_t bad_sym
 		return ReportStatus{SYZSIG_EINVAL, "uncovered_pcs: the symbols are not sorted by start"};
 	return report_ok();
 }
+
+// syzsig_file_set_dev before the frames are looked at (they are device memory)
+inline ReportStatus file_set_args(const void* ctx, const uint32_t* d_cov_file, const int32_t* d_cov_line,
+                                  const uint32_t* d_cov_func, uint64_t ncov, const uint32_t* d_unc_file,
+                                  const int32_t* d_unc_line, const uint32_t* d_unc_func, uint64_t nunc, uint64_t nfiles,
+                                  uint64_t nfuncs, const uint32_t* d_nlines, const uint64_t* d_off, const int32_t* d_line,
+                                  const uint8_t* d_covered, uint64_t cap, const uint32_t* d_shown,
+                                  const uint32_t* d_coverage)
+{
+	if (!ctx)
+		return ReportStatus{SYZSIG_EINVAL, "file_set: NULL context"};
+	if (!d_off || (ncov && (!d_cov_file || !d_cov_line || !d_cov_func)) ||
+	    (nunc && (!d_unc_file || !d_unc_line || !d_unc_func)) || (cap && (!d_line || !d_covered)))
+		return ReportStatus{SYZSIG_EINVAL, "file_set: NULL argument"};
+	if ((d_shown != nullptr) != (d_nlines != nullptr) || (d_coverage != nullptr) != (d_nlines != nullptr))
+		return ReportStatus{SYZSIG_EINVAL, "file_set: the walk needs d_nlines, d_shown and d_coverage, all or none"};
+	if (nfiles >= kReportMaxCount || nfuncs >= kReportMaxCount)
+		return ReportStatus{SYZSIG_ERANGE, "file_set: 2^32 or more files or functions"};
+	if (ncov >= kReportMaxPcs || nunc >= kReportMaxPcs || ncov + nunc >= kReportMaxPcs)
+		return ReportStatus{SYZSIG_ERANGE, "file_set: 2^31 or more frames"};
+	if ((ncov || nunc) && (!nfiles || !nfuncs))
+		return ReportStatus{SYZSIG_EINVAL, "file_set: frames without files or functions"};
+	return report_ok();
+}
+
+// ... after the frames' ids were checked: `bad_file` file ids >= nfiles, `bad_func` function ids >= nfuncs
+inline ReportStatus file_set_frames_status(uint64_t bad_file, uint64_t bad_func)
+{
+	if (bad_file)
+		return ReportStatus{SYZSIG_EINVAL, "file_set: a file id is not below nfiles"};
+	if (bad_func)
+		return ReportStatus{SYZSIG_EINVAL, "file_set: a function id is not below nfuncs"};
+	return report_ok();
+}
+
+// ... and once the lists are known, before any is written: `entries` (file, line) pairs in all
+inline ReportStatus file_set_cap_status(uint64_t entries, uint64_t cap)
+{
+	if (cap < entries)
+		return ReportStatus{SYZSIG_ERANGE, "file_set: cap is below the entries of the files' lists"};
+	return report_ok();
+}
+
+// fileSet's sort key of a (line, covered) pair inside its file: lines in signed
+// order (Go's int), a line's covered entry directly before its uncovered one.
+// 33 bits; two keys are entries of one line iff they agree above bit 0.
+SYZ_HD uint64_t file_set_key(int32_t line, bool covered)
+{
+	return (uint64_t)((uint32_t)line ^ 0x80000000u) << 1 | (covered ? 0u : 1u);
+}
+SYZ_HD int32_t file_set_key_line(uint64_t key) { return (int32_t)((uint32_t)(key >> 1) ^ 0x80000000u); }
+SYZ_HD bool file_set_key_covered(uint64_t key) { return !(key & 1); }
+
+// the walk of cover.go:131-143 consumes an entry only at `line == i + 1` with
+// i < nlines: an entry can be shown iff 1 <= line <= nlines (i32 against u32: in 64 bits)
+SYZ_HD bool file_set_line_within(int32_t line, uint32_t nlines) { return (int64_t)line <= (int64_t)nlines; }
+
+// A file whose list holds more entries than this is written and walked by a
+// workgroup, a shorter one by a wave.
+constexpr uint32_t kFileSetWaveEntries = 256;
+SYZ_HD bool file_set_block_path(uint64_t entries) { return entries > kFileSetWaveEntries; }
 
 // A handled function whose call sites number more than this is walked by a
 // workgroup, a shorter range by the wave that found it.

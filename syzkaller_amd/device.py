@@ -367,6 +367,23 @@ class Device:
         from . import report
         return report.report_stats(self)
 
+    def report_frames(self, covered, uncovered, files=(), funcs=()):
+        """Symbolized frames as the file_set kernels read them
+        (syzkaller_amd.report.Frames): File and Func interned to dense ids."""
+        from . import report
+        return report.Frames(self, covered, uncovered, files, funcs)
+
+    def file_set(self, frames, nlines=None, cap=None):
+        """fileSet and the line walk's Coverage, syz-manager/cover.go:129-193, as
+        CSR over the files (syzkaller_amd.report.file_set)."""
+        from . import report
+        return report.file_set(frames, nlines, cap)
+
+    def file_set_stats(self):
+        """The paths of the last file_set call (syzsig_file_set_stats)."""
+        from . import report
+        return report.file_set_stats(self)
+
     # ---------------------------------------------------------------- executor output ingest
     def ingest_exec_output(self, out, prog_off, prog_call, call_any, call_num=None, want_cover=False):
         """pkg/ipc/ipc.go:328-468 readOutCoverage over a batch of executor output

@@ -2,11 +2,12 @@
 numeric part of syz-manager/html.go and syz-manager/cover.go --
 collectSyscallInfo (html.go:135-149), httpCover's selection (html.go:202-212),
 RestorePC / previousInstructionPC / httpRawCover's sort (html.go:319-331,
-cover.go:99-104, :394-411) and uncoveredPcsInFuncs (cover.go:254-304).
+cover.go:99-104, :394-411), uncoveredPcsInFuncs (cover.go:254-304), fileSet
+(cover.go:162-193) and the line walk's Coverage count (cover.go:129-148).
 
 The text tools stay with the caller: objdump, nm, readelf, addr2line, the
 source files and the HTML template.  Call names are interned to dense ids by
-Corpus; PCs are numpy / torch integers.  Everything is computed by libsyzsig's
+Corpus, file and function names by Frames; PCs are numpy / torch integers.  Everything is computed by libsyzsig's
 kernels (csrc/report.hip); torch owns the buffers.
 """
 import ctypes
@@ -19,7 +20,8 @@ from ._lib import check
 from .signal import Cover
 
 __all__ = ["ARCH", "Corpus", "call_cover", "syscall_info", "cover_for", "report_pcs", "raw_cover_text",
-           "all_cover_pcs", "sort_symbols", "uncovered_pcs", "report_stats"]
+           "all_cover_pcs", "sort_symbols", "uncovered_pcs", "report_stats", "Frames", "file_set", "file_set_dict",
+           "file_set_stats", "parse_file_nlines", "file_order", "cover_files"]
 
 ARCH = {"amd64": _lib.SYZSIG_ARCH_AMD64, "386": _lib.SYZSIG_ARCH_386, "arm64": _lib.SYZSIG_ARCH_ARM64,
         "arm": _lib.SYZSIG_ARCH_ARM, "ppc64le": _lib.SYZSIG_ARCH_PPC64LE}
@@ -219,3 +221,189 @@ def report_stats(dev):
     out = (ctypes.c_uint64 * 4)()
     check(dev.L.syzsig_report_stats(dev.eng.h, out))
     return tuple(int(x) for x in out)
+
+
+# ---- fileSet and the per-file Coverage (cover.go:129-193) ----
+
+def _ids(dev, a, what):
+    """dense ids or lines as an int32 tensor on the device (u32 ids travel as the same bits)"""
+    if torch.is_tensor(a):
+        if a.element_size() != 4 or a.is_floating_point():
+            raise ValueError(f"{what} is a 32-bit integer tensor")
+        return a.reshape(-1).to(dev.dev).contiguous().view(torch.int32)
+    a = np.asarray(a)
+    if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 32)):
+        raise ValueError(f"{what} does not fit 32 bits")
+    a = np.ascontiguousarray(a.astype(np.int64).astype(np.uint32).reshape(-1))
+    return torch.from_numpy(a.view(np.int32)).to(dev.dev)
+
+
+def _is_interned(x):
+    return isinstance(x, tuple) and len(x) == 3 and all(hasattr(a, "dtype") for a in x)
+
+
+class Frames:
+    """coveredFrames and uncoveredFrames ([]symbolizer.Frame) as the file_set
+    kernels read them: per list three parallel arrays on the device -- dense
+    file ids, lines (int32) and dense function ids.  A list is an iterable of
+    (File, Line, Func) tuples, whose names are interned here as Corpus interns
+    call names (first-seen order over covered, then uncovered; names may be
+    given up front), or a tuple (file_ids, lines, func_ids) of arrays / tensors
+    that the caller interned, and then files / funcs give the names, or just
+    their counts.  funcs is keyed by the name alone, as the Go map is: one name
+    is one id whatever its file."""
+
+    def __init__(self, dev, covered, uncovered, files=(), funcs=()):
+        self.dev = dev
+        self.files, self.nfiles = (None, int(files)) if isinstance(files, int) else (list(files), None)
+        self.funcs, self.nfuncs = (None, int(funcs)) if isinstance(funcs, int) else (list(funcs), None)
+        self.file_id = {f: i for i, f in enumerate(self.files or ())}
+        self.func_id = {f: i for i, f in enumerate(self.funcs or ())}
+        self.cov = self._list(covered)
+        self.unc = self._list(uncovered)
+        if self.nfiles is None:
+            self.nfiles = len(self.files)
+        if self.nfuncs is None:
+            self.nfuncs = len(self.funcs)
+
+    def _intern(self, names, ids, name, what):
+        if names is None:
+            raise ValueError(f"frames with {what} names need the names' list, not a count")
+        i = ids.get(name)
+        if i is None:
+            i = ids[name] = len(names)
+            names.append(name)
+        return i
+
+    def _list(self, frames):
+        if _is_interned(frames):
+            t = (_ids(self.dev, frames[0], "file ids"), _ids(self.dev, frames[1], "lines"),
+                 _ids(self.dev, frames[2], "function ids"))
+            if not t[0].numel() == t[1].numel() == t[2].numel():
+                raise ValueError("a frame has a file, a line and a function")
+            return t
+        rows = [tuple(r) for r in frames]
+        a = np.empty((3, len(rows)), np.int64)
+        for i, (file, line, func) in enumerate(rows):
+            a[0, i] = self._intern(self.files, self.file_id, file, "file")
+            a[1, i] = int(line)
+            a[2, i] = self._intern(self.funcs, self.func_id, func, "function")
+        return _ids(self.dev, a[0], "file ids"), _ids(self.dev, a[1], "lines"), _ids(self.dev, a[2], "function ids")
+
+    @property
+    def ncov(self):
+        return self.cov[0].numel()
+
+    @property
+    def nunc(self):
+        return self.unc[0].numel()
+
+
+def _nlines_tensor(frames, nlines):
+    if isinstance(nlines, dict):
+        if frames.files is None:
+            raise ValueError("nlines by name needs the files' names")
+        nlines = [nlines.get(f, 0) for f in frames.files]  # (a file without a count shows nothing)
+    t = _ids(frames.dev, nlines, "nlines")
+    if t.numel() != frames.nfiles:
+        raise ValueError("nlines has one count per file")
+    return t
+
+
+def file_set(frames, nlines=None, cap=None):
+    """syzsig_file_set_dev: fileSet(covered, uncovered) (cover.go:162-193) as
+    CSR over the interned files, and with nlines the walk of cover.go:129-148.
+    Returns device tensors (off int64[nfiles + 1], line int32[...], covered
+    uint8[...], shown, coverage): file f's sorted (line, covered) list is
+    line / covered[off[f]:off[f + 1]]; shown[f] = the entries the walk
+    consumes, coverage[f] = templateFile.Coverage (both None without nlines).
+    nlines: {file: len(parseFile(file))} or one count per file id."""
+    dev = frames.dev
+    nf = frames.nfiles
+    cap = frames.ncov + frames.nunc if cap is None else int(cap)
+    off = torch.zeros(nf + 1, dtype=torch.int64, device=dev.dev)
+    line = torch.empty(cap, dtype=torch.int32, device=dev.dev)
+    covered = torch.empty(cap, dtype=torch.uint8, device=dev.dev)
+    nl = shown = coverage = None
+    if nlines is not None and nf:  # (no files: nothing to walk, and nothing to point at)
+        nl = _nlines_tensor(frames, nlines)
+        shown = torch.zeros(nf, dtype=torch.int32, device=dev.dev)
+        coverage = torch.zeros(nf, dtype=torch.int32, device=dev.dev)
+    dev.sync_stream()
+    check(dev.L.syzsig_file_set_dev(dev.eng.h, _p(frames.cov[0]), _p(frames.cov[1]), _p(frames.cov[2]), frames.ncov,
+                                    _p(frames.unc[0]), _p(frames.unc[1]), _p(frames.unc[2]), frames.nunc, nf,
+                                    frames.nfuncs, _p(nl), ctypes.c_void_p(off.data_ptr()), _p(line), _p(covered), cap,
+                                    _p(shown), _p(coverage)))
+    n = int(off[-1])
+    if nlines is not None and not nf:
+        shown = torch.zeros(0, dtype=torch.int32, device=dev.dev)
+        coverage = torch.zeros(0, dtype=torch.int32, device=dev.dev)
+    return off, line[:n], covered[:n], shown, coverage
+
+
+def file_set_dict(frames, cap=None):
+    """fileSet's Go map: {file: [(line, covered), ...]} with only the files that
+    have entries (names, or ids when the frames came interned without names)."""
+    off, line, covered, _, _ = file_set(frames, cap=cap)
+    off, line, covered = off.cpu().numpy(), line.cpu().numpy().tolist(), covered.cpu().numpy().astype(bool).tolist()
+    return {(frames.files[f] if frames.files is not None else f):
+            list(zip(line[off[f]:off[f + 1]], covered[off[f]:off[f + 1]]))
+            for f in np.flatnonzero(np.diff(off)).tolist()}
+
+
+def file_set_stats(dev):
+    """(uncovered frames kept by the funcs filter, files of more than
+    SYZSIG_FILESET_TILE frames, merge passes, entries written) of the last
+    file_set call (syzsig_file_set_stats)."""
+    out = (ctypes.c_uint64 * 4)()
+    check(dev.L.syzsig_file_set_stats(dev.eng.h, out))
+    return tuple(int(x) for x in out)
+
+
+def parse_file_nlines(data):
+    """len(parseFile(f)) for a file's bytes (cover.go:195-214): one line per
+    '\n', and one more when bytes follow the last '\n'."""
+    data = bytes(data)
+    return data.count(b"\n") + (1 if data and not data.endswith(b"\n") else 0)
+
+
+def file_order(names):
+    """The names as sort.Sort(templateFileArray) leaves them (cover.go:427-440):
+    names that start with '.' -- include files -- go below the others, each
+    group ascending; the empty name compares as a plain string."""
+    return sorted(names, key=lambda n: (n[:1] == ".", n))
+
+
+def cover_files(dev, cover_pcs, base, arch, sym_start, sym_end, all_cover, symbolize, nlines, files=(), funcs=()):
+    """generateCoverHTML's numeric path (cover.go:99-158), one device call per
+    step: report_pcs -> uncovered_pcs -> symbolize(covered PCs),
+    symbolize(uncovered PCs) -> file_set with the walk.  symbolize(pcs) takes
+    an int64 device tensor (u64 bits) and returns the frames of those PCs as
+    Frames takes a list -- (File, Line, Func) tuples, or three arrays interned
+    against files / funcs; File is the name the page shows (the common prefix
+    is text and stays with the caller).  Returns the page's files in
+    templateFileArray's order: dicts with ID (hash.String(Name), from the
+    batch hash), Name, Coverage, shown, and line / covered numpy arrays of the
+    file's sorted list.  No covered frames: ValueError, as Go's "does not have
+    debug info"."""
+    from . import hashing
+
+    order, _ = report_pcs(dev, cover_pcs, base, arch)
+    unc = uncovered_pcs(dev, sym_start, sym_end, all_cover, order)
+    frames = Frames(dev, symbolize(order), symbolize(unc), files, funcs)
+    if frames.ncov == 0:
+        raise ValueError("no covered frames: the kernel object does not have debug info")
+    if frames.files is None:
+        raise ValueError("cover_files needs the files' names")
+    off, line, covered, shown, coverage = file_set(frames, nlines)
+    off, line, covered = off.cpu().numpy(), line.cpu().numpy(), covered.cpu().numpy().astype(bool)
+    shown, coverage = shown.cpu().numpy(), coverage.cpu().numpy()
+    have = np.flatnonzero(np.diff(off)).tolist()
+    names = [frames.files[f].encode() for f in have]
+    noff = np.zeros(len(names) + 1, np.int64)
+    np.cumsum([len(n) for n in names], out=noff[1:])
+    sigs = hashing.hash_batch(dev, b"".join(names), noff).cpu().numpy()
+    by_name = {frames.files[f]: {"ID": hashing.to_string(sigs[k]), "Name": frames.files[f], "Coverage": int(coverage[f]),
+                                 "shown": int(shown[f]), "line": line[off[f]:off[f + 1]],
+                                 "covered": covered[off[f]:off[f + 1]]} for k, f in enumerate(have)}
+    return [by_name[n] for n in file_order(list(by_name))]
