@@ -832,6 +832,99 @@ int syzsig_number_sigs_dev(syzsig_ctx* ctx, const syzsig_sigset* known, const ui
 int syzsig_hub_sync_dev(syzsig_ctx* ctx, syzsig_sigset** hub_corpus, const uint8_t* d_sig, uint64_t n,
                         uint8_t* d_add, uint8_t* d_del_sig, uint64_t del_cap, uint64_t* ndel);
 
+/* ---- pkg/db/db.go:177-265: db.Open's read side -- deserializeDB over the
+ * file's bytes: corpus.db of syz-manager (manager.go:185-243), the databases of
+ * syz-hub (state.go:85-91), tools/syz-db.  The write side (serializeRecord's
+ * compressor, compact, Flush) stays with the caller. ----
+ * Three steps: the frames on the host, the values on the device, the map's
+ * last-write-wins on the device.  (d_out, d_out_off) of the second is what
+ * syzsig_hash_dev takes. */
+/* deserializeHeader and the frame of every deserializeRecord (db.go:203-257) of
+ * the host buffer data[0 .. nbytes); no context and no device.  The chain of
+ * lengths is walked, the compressed values are not read.  *version = the user
+ * version (0 for a version-1 header, the empty file, a bad header); *n = the
+ * records framed whole inside the file before the walk ended; *ended = how:
+ *   SYZSIG_DB_END_EOF         the file ended at a record boundary (:187-189), or is empty (:206-208)
+ *   SYZSIG_DB_END_BAD_HEADER  magic != 0xbaddb, version 0 or > 2, or the file ends inside the header:
+ *                             no record (:179-183)
+ *   SYZSIG_DB_END_BAD_MAGIC   a record that does not start with 0xfee1bad (:234-237)
+ *   SYZSIG_DB_END_TRUNCATED   the file ends inside a record: a field, a key or a value runs past it
+ * Record i: its key is data[key_off[i] .. + key_len[i]), seq[i]; its value's raw
+ * DEFLATE stream data[val_off[i] .. + val_len[i]), both 0 for a delete (seq ==
+ * ^0, :250-252) and for an empty value (valLen == 0, :257).  Every length is
+ * checked against the bytes left before it is used: a key length of 0xffffffff
+ * is a truncated record.  cap = the room of the five arrays in records; below
+ * *n: SYZSIG_ERANGE with *n set and nothing else written (NULL arrays with
+ * cap = 0: the sizing call).  SYZSIG_EINVAL: a NULL version, n or ended, a NULL
+ * data with nbytes > 0, NULL arrays with records to write. */
+#define SYZSIG_DB_END_EOF 0
+#define SYZSIG_DB_END_BAD_HEADER 1
+#define SYZSIG_DB_END_BAD_MAGIC 2
+#define SYZSIG_DB_END_TRUNCATED 3
+int syzsig_db_scan(const uint8_t* data, uint64_t nbytes, uint64_t cap, uint64_t* version, uint64_t* n,
+                   uint32_t* ended, uint64_t* key_off, uint32_t* key_len, uint64_t* seq, uint64_t* val_off,
+                   uint32_t* val_len);
+/* flate.NewReader + ioutil.ReadAll (db.go:258-259) over a batch: stream i is the
+ * raw DEFLATE (RFC 1951) bytes d_src[src_off[i] .. + src_len[i]), at any byte
+ * alignment; an entry of length 0 is skipped (status OK, no output: the empty
+ * value).  Stream i's output is d_out[out_off[i] .. out_off[i + 1]) (d_out_off
+ * has n + 1 entries, out_off[0] = 0), *out_bytes = out_off[n]; d_status[i]:
+ *   SYZSIG_INFLATE_OK
+ *   SYZSIG_INFLATE_TRUNCATED  the input ended before the final block's end
+ *   SYZSIG_INFLATE_INVALID    block type 3; a stored LEN != ~NLEN; HLIT > 286 or HDIST > 30; an
+ *                             over-subscribed code; an incomplete one other than the single one-bit
+ *                             code; a repeat with nothing to repeat or past HLIT + HDIST; no
+ *                             end-of-block code; literal/length symbols 286, 287; distance symbols
+ *                             30, 31; a distance that reaches before this stream's output
+ *   SYZSIG_INFLATE_TRAILING   bytes left after the final block.  (The reference's answer here
+ *                             depends on its bufio.Reader's fill; its writer never produces one.
+ *                             This class is this library's decision: DESIGN.md.)
+ *   SYZSIG_INFLATE_TOO_LONG   more than SYZSIG_INFLATE_MAX_OUT bytes of output
+ * the first one met in stream order; the decoder is pinned to zlib 1.2.11's
+ * inflate() wherever RFC 1951 leaves a choice (csrc/inflate_core.h).  A stream
+ * that is not OK has length 0 in d_out_off and disturbs no other.
+ * out_cap = the room of d_out.  Below *out_bytes: SYZSIG_ERANGE with *out_bytes
+ * set and nothing else written.  A NULL d_out with out_cap = 0 is the sizing
+ * call: SYZSIG_OK, d_out_off and d_status written as the full call writes them,
+ * no output.  n = 0 writes out_off[0] = 0.
+ * SYZSIG_EINVAL, nothing written: a NULL argument, a stream's range that passes
+ * nbytes (checked on device, overflow-safe, before any byte of d_src is read).
+ * SYZSIG_ERANGE, nothing written: more than 2^25 streams.
+ * Reads: as syzsig_hash_dev, no byte outside a stream's range is ever loaded;
+ * the decoder loads single bytes.  Every loop over input is bounded by the
+ * stream's length and every write by the extent the counting pass computed.
+ * One lane decodes one stream (counting pass, scan, writing pass);
+ * SYZSIG_INFLATE_LONG: a stream of more compressed bytes than this is left to a
+ * second launch that takes only such streams, as SYZSIG_HASH_LONG. */
+#define SYZSIG_INFLATE_OK 0
+#define SYZSIG_INFLATE_TRUNCATED 1
+#define SYZSIG_INFLATE_INVALID 2
+#define SYZSIG_INFLATE_TRAILING 3
+#define SYZSIG_INFLATE_TOO_LONG 4
+#define SYZSIG_INFLATE_MAX_OUT SYZSIG_HASH_MAX_MSG
+#define SYZSIG_INFLATE_LONG 4096
+int syzsig_inflate_dev(syzsig_ctx* ctx, const uint8_t* d_src, uint64_t nbytes, const uint64_t* d_src_off,
+                       const uint32_t* d_src_len, uint64_t n, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                       uint8_t* d_status, uint64_t* out_bytes);
+/* The paths of the last syzsig_inflate_dev call (its counting pass): out[0] =
+ * streams decoded by the first launch, out[1] = streams on the long list,
+ * out[2] = stored blocks, out[3] = fixed blocks in the low and dynamic blocks
+ * in the high 32 bits. */
+int syzsig_inflate_stats(syzsig_ctx* ctx, uint64_t out[4]);
+/* deserializeDB's loop over the records (db.go:185-200) as a map from key to
+ * the last write: d_sig = the n records' keys as 20-byte Sigs (the manager and
+ * the hub only write hash.String keys, 40 hex characters: the caller parses
+ * them; a database with any other key is replayed by the caller), d_seq their
+ * seqs, nvalid <= n = the records before the first one that failed (its value's
+ * status, or the scan's end).  live[i] = 1 iff i < nvalid, no record in
+ * (i, nvalid) has record i's key, and seq[i] != ^0: the records of db.Records.
+ * *nlive = their number = len(db.Records); *uncompacted = nvalid (:194).
+ * One sort of (Sig, index), the Sig sets' (SYZSIG_SIGSET_TILE), and the last of
+ * each run.  At most 2^25 records (SYZSIG_ERANGE).  All of d_live is written,
+ * after everything that can fail. */
+int syzsig_db_live_dev(syzsig_ctx* ctx, const uint8_t* d_sig, const uint64_t* d_seq, uint64_t n, uint64_t nvalid,
+                       uint8_t* d_live, uint64_t* nlive, uint64_t* uncompacted);
+
 /* ---- prog/prio.go:133-245: call-to-call priorities over the whole corpus and
  * the ChoiceTable (the numeric part; the program model stays with the caller) ----
  * N = len(target.Syscalls); a matrix is N * N row-major.  Every result is what

@@ -45,6 +45,11 @@ SYZSIG_HASH_MAX_MSG = 1 << 28  # syzsig_hash_dev: the longest message
 SYZSIG_HASH_STAGE = 32768  # ... a wave's span up to this is staged in LDS (sigs.hip)
 SYZSIG_HASH_LONG = 4096  # ... a message past this goes to the second launch
 SYZSIG_SIGSET_TILE = 2048  # the sort tile of a batch of Sigs (sigs.hip)
+SYZSIG_DB_END_EOF, SYZSIG_DB_END_BAD_HEADER, SYZSIG_DB_END_BAD_MAGIC, SYZSIG_DB_END_TRUNCATED = range(4)  # db_scan
+(SYZSIG_INFLATE_OK, SYZSIG_INFLATE_TRUNCATED, SYZSIG_INFLATE_INVALID, SYZSIG_INFLATE_TRAILING,
+ SYZSIG_INFLATE_TOO_LONG) = range(5)  # syzsig_inflate_dev's d_status
+SYZSIG_INFLATE_MAX_OUT = SYZSIG_HASH_MAX_MSG  # ... the longest output of one stream
+SYZSIG_INFLATE_LONG = 4096  # ... a stream of more compressed bytes goes to the second launch (db.hip)
 SYZSIG_PRIO_MAX_CALLS = 16384  # syzsig_calc_prios_dev: len(target.Syscalls) at most (one LDS row, prio.hip)
 SYZSIG_PRIO_SPLIT = 4096  # ... a call with more occurrences has its row counted in slices
 SYZSIG_FILESET_TILE = 2048  # syzsig_file_set_dev: a file of more frames leaves the one-workgroup LDS sort (report.hip)
@@ -189,6 +194,11 @@ SIGNATURES = {
     "syzsig_sigset_export_dev": (c_int, [_P, _P, _P, c_uint64, POINTER(c_uint64)]),
     "syzsig_number_sigs_dev": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, POINTER(c_uint64)]),
     "syzsig_hub_sync_dev": (c_int, [_P, _PP, _P, c_uint64, _P, _P, c_uint64, POINTER(c_uint64)]),
+    "syzsig_db_scan": (c_int, [_P, c_uint64, c_uint64, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32), _P, _P, _P,
+                               _P, _P]),
+    "syzsig_inflate_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, _P, POINTER(c_uint64)]),
+    "syzsig_inflate_stats": (c_int, [_P, _P]),
+    "syzsig_db_live_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, POINTER(c_uint64), POINTER(c_uint64)]),
     "syzsig_calc_prios_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, c_uint64, c_uint64, _P, _P]),
     "syzsig_static_prio_finish_dev": (c_int, [_P, _P, c_uint64]),
     "syzsig_choice_table_dev": (c_int, [_P, _P, _P, c_uint64, _P]),

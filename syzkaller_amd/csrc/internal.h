@@ -209,7 +209,10 @@ enum WsSlot : int {
 	kWsRcMeta = 75,
 	kWsRcStage = 76,
 	kWsRcStage2 = 77,
-	kWsCount = 78,
+	// db.hip: the long streams' list | the statuses, lengths and offsets held back until the call's end
+	kWsInfList = 78,
+	kWsInfMeta = 79,
+	kWsCount = 80,
 };
 
 // the debug flags that change only the path taken, never a result
@@ -276,6 +279,7 @@ struct syzsig_ctx {
 	uint64_t pq_stats[4] = {0, 0, 0, 0};  // syzsig_prio_stats: the last calc_prios call's paths (prio.hip)
 	uint64_t rc_stats[4] = {0, 0, 0, 0};  // syzsig_report_stats: the last coverage-report call's paths (report.hip)
 	uint64_t fs_stats[4] = {0, 0, 0, 0};  // syzsig_file_set_stats: the last file_set call's paths (report.hip)
+	uint64_t if_stats[4] = {0, 0, 0, 0};  // syzsig_inflate_stats: the last inflate call's paths (db.hip)
 	bool hash_stage = true;              // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
 };
 

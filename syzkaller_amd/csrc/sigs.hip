@@ -1,6 +1,8 @@
 // sigs.hip -- corpus identity on device: pkg/hash over a batch of programs
 // (syzsig_hash_dev) and the sets keyed by hash.Sig (syzsig_sigset_*,
-// syzsig_number_sigs_dev, syzsig_hub_sync_dev).
+// syzsig_number_sigs_dev, syzsig_hub_sync_dev), and on the same sort the
+// last-write-wins of pkg/db's replay (syzsig_db_live_dev; the rest of pkg/db is
+// db.hip).
 //
 // References:
 //   pkg/hash/hash.go:14-26    type Sig [sha1.Size]byte; Hash = sha1 of the pieces
@@ -12,6 +14,8 @@
 //       in hubCorpus), Del = hubCorpus \ corpus (then deleted)
 //   syz-manager/manager.go:976-1025    NewInput: sig := hash.String(a.Prog) keys
 //       mgr.corpus (numberSigs gives syzsig_manager_new_input_batch its keys)
+//   pkg/db/db.go:185-200   deserializeDB's loop: a delete (seq == ^0) removes the
+//       key, any other record overwrites it
 //
 // Hashing.  SHA-1 is serial inside a message, so a lane owns a message and a
 // wave 64 consecutive ones, whose bytes are one contiguous span of d_data:
@@ -44,6 +48,8 @@
 //   k_sg_merge     set and new keys into a new buffer by rank: a key goes to its
 //                  index plus the keys of the other list below it (the lists
 //                  are disjoint), the bijection of k_su_merge
+//   k_sg_last      (db_live) per sorted key: the tail of its run is the key's last
+//                  record; it is live unless it is a delete
 // Outputs are staged in the workspace and the new buffer is allocated before
 // anything of the caller's is written; the set takes the new buffer last.
 #include <algorithm>
@@ -52,6 +58,7 @@
 #include "segsort.h"
 #include "sha1.h"
 #include "sigs_args.h"
+#include "db_args.h"
 
 struct syzsig_sigset {
 	syzsig_ctx* ctx = nullptr;
@@ -393,6 +400,24 @@ __global__ __launch_bounds__(256) void k_sg_number(const uint64_t* __restrict__ 
 			is_known[k] = sg_find(known, m, x) != m;
 		}
 	}
+}
+
+// live[row] = 1 for the last row of every distinct Sig unless its seq is `deleted`, else 0: every
+// row of the batch is written once.  The live rows are counted into *cnt.
+__global__ __launch_bounds__(256) void k_sg_last(const uint64_t* __restrict__ b, uint64_t n,
+                                                 const uint64_t* __restrict__ seq, uint64_t deleted, uint8_t* live,
+                                                 unsigned long long* cnt)
+{
+	const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
+	uint64_t k = 0;
+	for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += T) {
+		const SgT x = SgKey::get(b, j);
+		const uint32_t row = sg_row(x);
+		const bool lv = (j + 1 == n || !sg_same(x, SgKey::get(b, j + 1))) && seq[row] != deleted;
+		live[row] = lv;
+		k += lv;
+	}
+	block_count(cnt, k);
 }
 
 // ---- host ----
@@ -742,5 +767,39 @@ extern "C" int syzsig_hub_sync_dev(syzsig_ctx* ctx, syzsig_sigset** hub, const u
 	SYZ_HIP(hipGetLastError());
 	SYZ_HIP(hipStreamSynchronize(s));
 	sg_commit(hub, made, ctx, nb.release(), distinct);
+	return SYZSIG_OK;
+}
+
+extern "C" int syzsig_db_live_dev(syzsig_ctx* ctx, const uint8_t* d_sig, const uint64_t* d_seq, uint64_t n,
+                                  uint64_t nvalid, uint8_t* d_live, uint64_t* nlive, uint64_t* uncompacted)
+{
+	SYZ_LOCK(ctx);
+	if (nlive)
+		*nlive = 0;
+	if (uncompacted)
+		*uncompacted = 0;
+	SYZ_ARGS(db_live_args(ctx, d_sig, d_seq, n, nvalid, d_live, nlive, uncompacted));
+	if (n == 0)
+		return SYZSIG_OK;
+	const hipStream_t s = ctx->stream;
+	uint8_t* row_live;
+	SYZ_TRY(ws_get(ctx, kWsSgOut, n + 256, (void**)&row_live));
+	SYZ_TRY(counters_reset(ctx));
+	SYZ_HIP(hipMemsetAsync(row_live, 0, n, s));  // (the rows from nvalid on)
+	if (nvalid) {
+		SgWork w;
+		SYZ_TRY(sg_work(ctx, nvalid, nvalid, &w));
+		const uint64_t* b;
+		uint64_t* spare;
+		SYZ_TRY(sg_sort(ctx, d_sig, nvalid, w, &b, &spare));
+		k_sg_last<<<grid_for(nvalid, 256), 256, 0, s>>>(b, nvalid, d_seq, kDbSeqDeleted, row_live,
+		                                                &ctx->d_cnt[kCntInserted]);
+		SYZ_HIP(hipGetLastError());
+	}
+	SYZ_TRY(counters_fetch(ctx));
+	SYZ_HIP(hipMemcpyAsync(d_live, row_live, n, hipMemcpyDeviceToDevice, s));
+	SYZ_HIP(hipStreamSynchronize(s));
+	*nlive = ctx->h_cnt[kCntInserted];
+	*uncompacted = nvalid;
 	return SYZSIG_OK;
 }
