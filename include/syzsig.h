@@ -1203,6 +1203,85 @@ int syzsig_synth_m0_shard_dev(syzsig_ctx* ctx, const syzsig_synth_cfg* cfg, uint
                               uint32_t nshards, uint32_t shard, uint32_t* d_elems, int8_t* d_prios, uint64_t cap,
                               uint64_t* n_out);
 
+/* ---- program text: the calls of a batch of programs (csrc/calls.hip) ----
+ *
+ * The heads of the lines of program text, and nothing else of it: the ordered
+ * call ids that target.Deserialize would give p.Calls[*].Meta.ID
+ * (prog/encoding.go:159-180, the parser of :740-828), or prog.CallSet's set
+ * (:836-869).  This does not parse arguments, it does not run validate(), and it
+ * does not run SanitizeCall: a program whose heads are well-formed but whose
+ * arguments are broken is reported OK here.  Deserialize stays with the caller
+ * for programs that arrive from outside.
+ *
+ * The name table of one target: names[name_off[i] .. name_off[i + 1]) is the name
+ * of call id i (host arrays, name_off[0] = 0, n + 1 offsets).  Open-addressed on
+ * a 64-bit hash of the bytes; a hit is the hash, the length and then the bytes.
+ * SYZSIG_EINVAL: a NULL argument, n = 0, an empty name, a duplicate name, offsets
+ * that decrease.  SYZSIG_ERANGE: more than 2^24 names. */
+typedef struct syzsig_calltab syzsig_calltab;
+int syzsig_calltab_make(syzsig_ctx* ctx, const uint8_t* names, const uint64_t* name_off, uint64_t n,
+                        syzsig_calltab** out);
+void syzsig_calltab_free(syzsig_calltab* tab);
+uint64_t syzsig_calltab_len(const syzsig_calltab* tab);
+/* Program i is d_data[off[i] .. off[i + 1]) (d_off has nprog + 1 entries; d_data
+ * is 16-byte aligned).  Lines are bufio.ScanLines': the runs between '\n' inside
+ * the program, a last run without '\n' if it is not empty, one trailing '\r'
+ * dropped; a line never passes off[i + 1].  A line of SYZSIG_PROGTEXT_MAX_LINE
+ * bytes or more before its '\n' ('\r' counted) fails its program with
+ * SYZSIG_PT_LINE_TOO_LONG.  Empty lines and lines that start with '#' are skipped.
+ * d_status[i] is the status of the program's first failing line and d_err_line[i]
+ * that line's 1-based number, skipped lines counted (0: no line to blame); a
+ * program that is not OK has an empty range in d_call_off and flag 0.
+ *   SYZSIG_PROGTEXT_DESERIALIZE  a line is I W* ( '=' W* I W* )? '(' from its first
+ *     byte (W: space or tab, I: one or more of [a-zA-Z0-9_$]), the name its last I.
+ *     SYZSIG_PT_BAD_IDENT: no identifier at the line's start or after the '=';
+ *     SYZSIG_PT_BAD_HEAD: the line ends where '=' or '(' is expected;
+ *     SYZSIG_PT_UNKNOWN_CALL: the name is not in the table (looked up before the
+ *     '('); SYZSIG_PT_BAD_HEAD: the next byte is not '('.  A program without call
+ *     lines is OK with no calls.  The ids are in line order; d_flag[i] = 1 when a
+ *     call of the program has d_enabled[id] == 0 ("contains a disabled syscall").
+ *   SYZSIG_PROGTEXT_CALLSET  the name is the line up to its first '(' -- none:
+ *     SYZSIG_PT_NO_BRACKET -- restarted behind its first '=' and the spaces (not
+ *     tabs) after it; empty: SYZSIG_PT_EMPTY_NAME; a program without calls:
+ *     SYZSIG_PT_NO_CALLS.  The ids are the distinct names found in the table,
+ *     ascending; d_flag[i] = supported | has_unknown << 1: has_unknown = some name
+ *     is not in the table, supported = !has_unknown and every id enabled.
+ * d_enabled: one byte per table entry, NULL = every call enabled.
+ * Count-then-write: *total = d_call_off[nprog].  cap = the room of d_call_id;
+ * below *total: SYZSIG_ERANGE with *total set and nothing else written.  A NULL
+ * d_call_id with cap = 0 is the sizing call: SYZSIG_OK, everything but the ids
+ * written.  nprog = 0 writes call_off[0] = 0.
+ * SYZSIG_EINVAL, nothing written: a NULL argument or table, a mode that is neither,
+ * offsets that decrease or pass nbytes.  SYZSIG_ERANGE, nothing written: more
+ * than 2^25 programs, 2^32 calls or more.
+ * The text is read twice (line starts counted, then parsed), 16 bytes per lane,
+ * SYZSIG_PROGTEXT_TILE bytes per workgroup staged in LDS with
+ * SYZSIG_PROGTEXT_WINDOW bytes behind them; a head that does not end inside the
+ * window after its line's start is left to a second launch.  CallSet's dedup is
+ * the shared segmented sort-unique, SYZSIG_PROGTEXT_SORT_TILE ids per tile. */
+#define SYZSIG_PROGTEXT_DESERIALIZE 0
+#define SYZSIG_PROGTEXT_CALLSET 1
+#define SYZSIG_PROGTEXT_MAX_LINE (1u << 20)
+#define SYZSIG_PROGTEXT_TILE 4096
+#define SYZSIG_PROGTEXT_WINDOW 256
+#define SYZSIG_PROGTEXT_SORT_TILE 2048
+#define SYZSIG_PT_OK 0
+#define SYZSIG_PT_LINE_TOO_LONG 1
+#define SYZSIG_PT_BAD_IDENT 2
+#define SYZSIG_PT_BAD_HEAD 3
+#define SYZSIG_PT_UNKNOWN_CALL 4
+#define SYZSIG_PT_NO_BRACKET 5
+#define SYZSIG_PT_EMPTY_NAME 6
+#define SYZSIG_PT_NO_CALLS 7
+int syzsig_prog_calls_dev(syzsig_ctx* ctx, const syzsig_calltab* tab, const uint8_t* d_data, uint64_t nbytes,
+                          const uint64_t* d_off, uint64_t nprog, uint32_t mode, const uint8_t* d_enabled,
+                          uint64_t* d_call_off, uint32_t* d_call_id, uint64_t cap, uint8_t* d_status,
+                          uint32_t* d_err_line, uint8_t* d_flag, uint64_t* total);
+/* The paths of the last syzsig_prog_calls_dev call: out[0] = lines seen, out[1] =
+ * lines skipped, out[2] = heads parsed in the window, out[3] = heads on the long
+ * list. */
+int syzsig_prog_calls_stats(syzsig_ctx* ctx, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,13 @@ SYZSIG_INFLATE_LONG = 4096  # ... a stream of more compressed bytes goes to the 
 SYZSIG_PRIO_MAX_CALLS = 16384  # syzsig_calc_prios_dev: len(target.Syscalls) at most (one LDS row, prio.hip)
 SYZSIG_PRIO_SPLIT = 4096  # ... a call with more occurrences has its row counted in slices
 SYZSIG_FILESET_TILE = 2048  # syzsig_file_set_dev: a file of more frames leaves the one-workgroup LDS sort (report.hip)
+SYZSIG_PROGTEXT_DESERIALIZE, SYZSIG_PROGTEXT_CALLSET = 0, 1  # syzsig_prog_calls_dev's mode (csrc/calls.hip)
+SYZSIG_PROGTEXT_MAX_LINE = 1 << 20  # ... a line of this many bytes or more fails its program (bufio.Scanner's buffer)
+SYZSIG_PROGTEXT_TILE = 4096  # ... the bytes of text a workgroup stages
+SYZSIG_PROGTEXT_WINDOW = 256  # ... and those behind them: a head that does not end there goes to the second launch
+SYZSIG_PROGTEXT_SORT_TILE = 2048  # ... CallSet's dedup: a program of more known calls leaves the one-workgroup LDS sort
+(SYZSIG_PT_OK, SYZSIG_PT_LINE_TOO_LONG, SYZSIG_PT_BAD_IDENT, SYZSIG_PT_BAD_HEAD, SYZSIG_PT_UNKNOWN_CALL,
+ SYZSIG_PT_NO_BRACKET, SYZSIG_PT_EMPTY_NAME, SYZSIG_PT_NO_CALLS) = range(8)  # syzsig_prog_calls_dev's d_status
 SYZSIG_ARCH_AMD64, SYZSIG_ARCH_386, SYZSIG_ARCH_ARM64, SYZSIG_ARCH_ARM, SYZSIG_ARCH_PPC64LE = range(5)  # report_pcs
 SYZSIG_INGEST_OK = 0
 SYZSIG_INGEST_ECOMPS = 8
@@ -199,6 +206,12 @@ SIGNATURES = {
     "syzsig_inflate_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, _P, POINTER(c_uint64)]),
     "syzsig_inflate_stats": (c_int, [_P, _P]),
     "syzsig_db_live_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, POINTER(c_uint64), POINTER(c_uint64)]),
+    "syzsig_calltab_make": (c_int, [_P, _P, _P, c_uint64, _PP]),
+    "syzsig_calltab_free": (None, [_P]),
+    "syzsig_calltab_len": (c_uint64, [_P]),
+    "syzsig_prog_calls_dev": (c_int, [_P, _P, _P, c_uint64, _P, c_uint64, c_uint32, _P, _P, _P, c_uint64, _P, _P, _P,
+                                      POINTER(c_uint64)]),
+    "syzsig_prog_calls_stats": (c_int, [_P, _P]),
     "syzsig_calc_prios_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, c_uint64, c_uint64, _P, _P]),
     "syzsig_static_prio_finish_dev": (c_int, [_P, _P, c_uint64]),
     "syzsig_choice_table_dev": (c_int, [_P, _P, _P, c_uint64, _P]),

@@ -212,7 +212,14 @@ enum WsSlot : int {
 	// db.hip: the long streams' list | the statuses, lengths and offsets held back until the call's end
 	kWsInfList = 78,
 	kWsInfMeta = 79,
-	kWsCount = 80,
+	// calls.hip: the tiles' line counts and bases, the programs' first lines and held-back outputs | the
+	// lines' starts and records | the long list | CallSet's raw ids and the sorted survivors
+	kWsPcMeta = 80,
+	kWsPcLines = 81,
+	kWsPcList = 82,
+	kWsPcStage = 83,
+	kWsPcStage2 = 84,
+	kWsCount = 85,
 };
 
 // the debug flags that change only the path taken, never a result
@@ -280,7 +287,8 @@ struct syzsig_ctx {
 	uint64_t rc_stats[4] = {0, 0, 0, 0};  // syzsig_report_stats: the last coverage-report call's paths (report.hip)
 	uint64_t fs_stats[4] = {0, 0, 0, 0};  // syzsig_file_set_stats: the last file_set call's paths (report.hip)
 	uint64_t if_stats[4] = {0, 0, 0, 0};  // syzsig_inflate_stats: the last inflate call's paths (db.hip)
-	bool hash_stage = true;              // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
+	uint64_t pc_stats[4] = {0, 0, 0, 0};  // syzsig_prog_calls_stats: the last prog_calls call's paths (calls.hip)
+	bool hash_stage = true;             // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
 };
 
 struct syzsig_set {
