@@ -834,8 +834,9 @@ int syzsig_hub_sync_dev(syzsig_ctx* ctx, syzsig_sigset** hub_corpus, const uint8
 
 /* ---- pkg/db/db.go:177-265: db.Open's read side -- deserializeDB over the
  * file's bytes: corpus.db of syz-manager (manager.go:185-243), the databases of
- * syz-hub (state.go:85-91), tools/syz-db.  The write side (serializeRecord's
- * compressor, compact, Flush) stays with the caller. ----
+ * syz-hub (state.go:85-91), tools/syz-db.  The write side (serializeRecord with
+ * its compressor, Save / Delete's no-op rules) follows below; files, Flush and
+ * compact's decisions are the caller's (syzkaller_amd/db.py restates them). ----
  * Three steps: the frames on the host, the values on the device, the map's
  * last-write-wins on the device.  (d_out, d_out_off) of the second is what
  * syzsig_hash_dev takes. */
@@ -924,6 +925,87 @@ int syzsig_inflate_stats(syzsig_ctx* ctx, uint64_t out[4]);
  * after everything that can fail. */
 int syzsig_db_live_dev(syzsig_ctx* ctx, const uint8_t* d_sig, const uint64_t* d_seq, uint64_t n, uint64_t nvalid,
                        uint8_t* d_live, uint64_t* nlive, uint64_t* uncompacted);
+
+/* ---- pkg/db/db.go:55-74, :147-175: the write side -- Save, Delete and
+ * serializeRecord over a batch.  What is pinned is what a reader depends on:
+ * the frame around a stream, which ops reach the log, and that zlib's inflate
+ * and syzsig_inflate_dev read every stream back to its value.  The stream's own
+ * bytes are this library's (compress/flate's differ between Go releases). ---- */
+/* The compressor of serializeRecord over a batch, the mirror image of
+ * syzsig_inflate_dev: value i is d_src[src_off[i] .. + src_len[i]), at any byte
+ * alignment; its raw DEFLATE (RFC 1951) stream is d_out[out_off[i] ..
+ * out_off[i + 1]) (n + 1 entries, out_off[0] = 0), *out_bytes = out_off[n].  A
+ * value of length 0 gets a stream of length 0 (valLen = 0, db.go:158-159).
+ * A stream is greedy LZ77 (matches of 3..258 bytes at distances <= 32768, found
+ * through a hash table of recent positions, every candidate verified byte by
+ * byte) in one final fixed-Huffman block, or, when that is not smaller, stored
+ * blocks of at most 65535 bytes, the last one final: at most
+ * len + 5 * ceil(len / 65535) bytes.  No sync-flush and no empty final block.
+ * A stream's bytes depend on the value's bytes alone -- not on its lane, its
+ * place or neighbours in the batch, its alignment or the launch that took it --
+ * and equal syzsig_deflate_host's (one shared core, csrc/deflate_core.h).
+ * out_cap = the room of d_out.  Below *out_bytes: SYZSIG_ERANGE with *out_bytes
+ * set and nothing else written.  A NULL d_out with out_cap = 0 is the sizing
+ * call: SYZSIG_OK, d_out_off written, no output.  n = 0 writes out_off[0] = 0.
+ * SYZSIG_EINVAL, nothing written: a NULL argument, a value's range that passes
+ * nbytes (checked on device, overflow-safe, before any byte of d_src is read).
+ * SYZSIG_ERANGE, nothing written: more than 2^25 values, or a value of more than
+ * SYZSIG_INFLATE_MAX_OUT bytes (it could never be read back).
+ * Reads: no byte outside a value's range is ever loaded; single bytes.  Every
+ * write is bounded by the extent the counting pass computed.  One lane
+ * compresses one value (counting pass, scan, writing pass), its hash table in
+ * LDS; SYZSIG_DEFLATE_LONG: a value of more bytes is left to a second launch
+ * that takes only such values, as SYZSIG_INFLATE_LONG. */
+#define SYZSIG_DEFLATE_LONG 4096
+int syzsig_deflate_dev(syzsig_ctx* ctx, const uint8_t* d_src, uint64_t nbytes, const uint64_t* d_src_off,
+                       const uint32_t* d_src_len, uint64_t n, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                       uint64_t* out_bytes);
+/* The paths of the last syzsig_deflate_dev call (its counting pass): out[0] =
+ * values compressed by the first launch, out[1] = values on the long list,
+ * out[2] = streams written stored, out[3] = streams written fixed. */
+int syzsig_deflate_stats(syzsig_ctx* ctx, uint64_t out[4]);
+/* The same compressor for one value in host memory; no context and no device
+ * (as syzsig_db_scan).  *out_len = the stream's size; cap below it:
+ * SYZSIG_ERANGE with *out_len set and nothing written (a NULL out with cap = 0:
+ * the sizing call).  SYZSIG_EINVAL: a NULL out_len, a NULL src with len > 0, a
+ * NULL out with cap > 0; SYZSIG_ERANGE: len above SYZSIG_INFLATE_MAX_OUT. */
+int syzsig_deflate_host(const uint8_t* src, uint64_t len, uint8_t* out, uint64_t cap, uint64_t* out_len);
+/* serializeRecord (db.go:147-175) over n records: d_sig their keys as 20-byte
+ * Sigs, d_seq their seqs, stream i = d_stream[stream_off[i] .. stream_off[i + 1])
+ * (syzsig_deflate_dev's outputs).  Record i is d_out[rec_off[i] .. rec_off[i + 1])
+ * (n + 1 entries), *out_bytes = rec_off[n]: u32 0xfee1bad, u32 40, the Sig as 40
+ * lower-case hex characters (hash.String), u64 seq, and unless seq == ^0 (a
+ * delete: 56 bytes) u32 stream length and the stream (an empty one: 60 bytes);
+ * little-endian.  The 16-byte file header is the caller's.  out_cap, the sizing
+ * call and SYZSIG_ERANGE as syzsig_deflate_dev.  SYZSIG_EINVAL, nothing written:
+ * a NULL argument, stream offsets that decrease or pass stream_bytes, a delete
+ * with a stream of non-zero length (the reference's panic, :153-155);
+ * SYZSIG_ERANGE: more than 2^25 records, a stream of 2^32 bytes or more. */
+int syzsig_db_records_dev(syzsig_ctx* ctx, const uint8_t* d_sig, const uint64_t* d_seq, uint64_t n,
+                          const uint8_t* d_stream, uint64_t stream_bytes, const uint64_t* d_stream_off, uint8_t* d_out,
+                          uint64_t out_cap, uint64_t* d_rec_off, uint64_t* out_bytes);
+/* Save and Delete (db.go:55-74) over m ops in order, against the live set of nl
+ * records (db.Records: distinct keys, no seq of ^0): Sigs, seqs and values
+ * (data, off) each, value i = data[off[i] .. off[i + 1]); an op with seq == ^0 is
+ * a Delete.  written[j] = 1 iff op j reaches the log: a Save unless its key is
+ * present with the same seq and equal bytes (:59-61), a Delete unless its key is
+ * absent (:68-70), where the state an op sees is what the last earlier row of
+ * its key -- op or live record -- left.  keep_live[i] / keep_op[j] = 1 for the
+ * rows of the new db.Records: per key its last written row (a live record
+ * counts as written), unless that is a Delete; the new Records in file order of
+ * the last write are the kept live records in their order, then the kept ops in
+ * theirs.  *nwritten, *nkeep_live, *nkeep_op their counts.  One sort of (Sig,
+ * row) over nl + m rows, the Sig sets' (SYZSIG_SIGSET_TILE), a look at each
+ * run's neighbours, and a byte compare where seq and length agree.
+ * SYZSIG_EINVAL, nothing written: a NULL argument, offsets that decrease or pass
+ * their nbytes, a Delete with a non-empty value, a live seq of ^0;
+ * SYZSIG_ERANGE: nl + m above 2^25.  Everything is written after everything
+ * that can fail. */
+int syzsig_db_apply_dev(syzsig_ctx* ctx, const uint8_t* d_live_sig, const uint64_t* d_live_seq, uint64_t nl,
+                        const uint8_t* d_live_data, uint64_t live_bytes, const uint64_t* d_live_off,
+                        const uint8_t* d_op_sig, const uint64_t* d_op_seq, uint64_t m, const uint8_t* d_op_data,
+                        uint64_t op_bytes, const uint64_t* d_op_off, uint8_t* d_written, uint8_t* d_keep_live,
+                        uint8_t* d_keep_op, uint64_t* nwritten, uint64_t* nkeep_live, uint64_t* nkeep_op);
 
 /* ---- prog/prio.go:133-245: call-to-call priorities over the whole corpus and
  * the ChoiceTable (the numeric part; the program model stays with the caller) ----

@@ -50,6 +50,7 @@ SYZSIG_DB_END_EOF, SYZSIG_DB_END_BAD_HEADER, SYZSIG_DB_END_BAD_MAGIC, SYZSIG_DB_
  SYZSIG_INFLATE_TOO_LONG) = range(5)  # syzsig_inflate_dev's d_status
 SYZSIG_INFLATE_MAX_OUT = SYZSIG_HASH_MAX_MSG  # ... the longest output of one stream
 SYZSIG_INFLATE_LONG = 4096  # ... a stream of more compressed bytes goes to the second launch (db.hip)
+SYZSIG_DEFLATE_LONG = 4096  # syzsig_deflate_dev: a value of more bytes goes to the second launch (db.hip)
 SYZSIG_PRIO_MAX_CALLS = 16384  # syzsig_calc_prios_dev: len(target.Syscalls) at most (one LDS row, prio.hip)
 SYZSIG_PRIO_SPLIT = 4096  # ... a call with more occurrences has its row counted in slices
 SYZSIG_FILESET_TILE = 2048  # syzsig_file_set_dev: a file of more frames leaves the one-workgroup LDS sort (report.hip)
@@ -206,7 +207,13 @@ SIGNATURES = {
     "syzsig_inflate_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, _P, POINTER(c_uint64)]),
     "syzsig_inflate_stats": (c_int, [_P, _P]),
     "syzsig_db_live_dev": (c_int, [_P, _P, _P, c_uint64, c_uint64, _P, POINTER(c_uint64), POINTER(c_uint64)]),
-    "syzsig_calltab_make": (c_int, [_P, _P, _P, c_uint64, _PP]),
+    "syzsig_deflate_dev": (c_int, [_P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint64, _P, POINTER(c_uint64)]),
+    "syzsig_deflate_stats": (c_int, [_P, _P]),
+    "syzsig_deflate_host": (c_int, [_P, c_uint64, _P, c_uint64, POINTER(c_uint64)]),
+    "syzsig_db_records_dev": (c_int, [_P, _P, _P, c_uint64, _P, c_uint64, _P, _P, c_uint64, _P, POINTER(c_uint64)]),
+    "syzsig_db_apply_dev": (c_int, [_P, _P, _P, c_uint64, _P, c_uint64, _P, _P, _P, c_uint64, _P, c_uint64, _P, _P, _P, _P,
+                                    POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "syzsig_calltab_make":(c_int, [_P, _P, _P, c_uint64, _PP]),
     "syzsig_calltab_free": (None, [_P]),
     "syzsig_calltab_len": (c_uint64, [_P]),
     "syzsig_prog_calls_dev": (c_int, [_P, _P, _P, c_uint64, _P, c_uint64, c_uint32, _P, _P, _P, c_uint64, _P, _P, _P,

@@ -151,6 +151,113 @@ inline ArgStatus inflate_room(uint64_t total, uint64_t out_cap, bool sizing)
 	return arg_ok();
 }
 
+// syzsig_deflate_dev before the ranges are looked at
+inline ArgStatus deflate_args(const void* ctx, const uint8_t* d_src, uint64_t nbytes, const uint64_t* d_src_off,
+                              const uint32_t* d_src_len, uint64_t n, const uint8_t* d_out, uint64_t out_cap,
+                              const uint64_t* d_out_off, const uint64_t* out_bytes)
+{
+	if (!ctx)
+		return ArgStatus{SYZSIG_EINVAL, "deflate: NULL context"};
+	if (!out_bytes || !d_out_off)
+		return ArgStatus{SYZSIG_EINVAL, "deflate: NULL argument"};
+	if (n > kInflateMaxBatch)
+		return ArgStatus{SYZSIG_ERANGE, "deflate: more than 2^25 values in one call"};
+	if (n && (!d_src_off || !d_src_len || (nbytes && !d_src)))
+		return ArgStatus{SYZSIG_EINVAL, "deflate: NULL argument"};
+	if (!d_out && out_cap)
+		return ArgStatus{SYZSIG_EINVAL, "deflate: NULL output with a capacity"};
+	return arg_ok();
+}
+
+// ... and after: `bad` ranges that pass nbytes, `huge` values past SYZSIG_INFLATE_MAX_OUT
+inline ArgStatus deflate_ranges_status(uint64_t bad, uint64_t huge)
+{
+	if (bad)
+		return ArgStatus{SYZSIG_EINVAL, "deflate: a value's range passes nbytes"};
+	if (huge)
+		return ArgStatus{SYZSIG_ERANGE, "deflate: a value is longer than SYZSIG_INFLATE_MAX_OUT"};
+	return arg_ok();
+}
+
+// ... and once the total is known (deflate and db_records).  sizing = a NULL d_out.
+inline ArgStatus write_room(uint64_t total, uint64_t out_cap, bool sizing, const char* who_range)
+{
+	if (!sizing && total > out_cap)
+		return ArgStatus{SYZSIG_ERANGE, who_range};
+	return arg_ok();
+}
+
+// syzsig_deflate_host, before the value is read
+inline ArgStatus deflate_host_args(const uint8_t* src, uint64_t len, const uint8_t* out, uint64_t cap,
+                                   const uint64_t* out_len, uint64_t max_len)
+{
+	if (!out_len || (len && !src) || (cap && !out))
+		return ArgStatus{SYZSIG_EINVAL, "deflate_host: NULL argument"};
+	if (len > max_len)
+		return ArgStatus{SYZSIG_ERANGE, "deflate_host: the value is longer than SYZSIG_INFLATE_MAX_OUT"};
+	return arg_ok();
+}
+
+// syzsig_db_records_dev before the offsets are looked at
+inline ArgStatus db_records_args(const void* ctx, const uint8_t* d_sig, const uint64_t* d_seq, uint64_t n,
+                                 const uint8_t* d_stream, uint64_t stream_bytes, const uint64_t* d_stream_off,
+                                 const uint8_t* d_out, uint64_t out_cap, const uint64_t* d_rec_off,
+                                 const uint64_t* out_bytes)
+{
+	if (!ctx || !out_bytes || !d_rec_off)
+		return ArgStatus{SYZSIG_EINVAL, "db_records: NULL argument"};
+	if (n > kSigsMaxBatch)
+		return ArgStatus{SYZSIG_ERANGE, "db_records: more than 2^25 records in one call"};
+	if (n && (!d_sig || !d_seq || !d_stream_off || (stream_bytes && !d_stream)))
+		return ArgStatus{SYZSIG_EINVAL, "db_records: NULL argument"};
+	if (!d_out && out_cap)
+		return ArgStatus{SYZSIG_EINVAL, "db_records: NULL output with a capacity"};
+	return arg_ok();
+}
+
+// ... and after: offsets that decrease or pass stream_bytes, deletes that carry a stream, streams of 2^32 bytes
+inline ArgStatus db_records_status(uint64_t bad, uint64_t del_with_val, uint64_t huge)
+{
+	if (bad)
+		return ArgStatus{SYZSIG_EINVAL, "db_records: the stream offsets decrease or pass stream_bytes"};
+	if (del_with_val)
+		return ArgStatus{SYZSIG_EINVAL, "db_records: deleting record with value"};
+	if (huge)
+		return ArgStatus{SYZSIG_ERANGE, "db_records: a stream of 2^32 bytes or more"};
+	return arg_ok();
+}
+
+// syzsig_db_apply_dev before anything on the device is looked at
+inline ArgStatus db_apply_args(const void* ctx, const uint8_t* d_live_sig, const uint64_t* d_live_seq, uint64_t nl,
+                               const uint8_t* d_live_data, uint64_t live_bytes, const uint64_t* d_live_off,
+                               const uint8_t* d_op_sig, const uint64_t* d_op_seq, uint64_t m, const uint8_t* d_op_data,
+                               uint64_t op_bytes, const uint64_t* d_op_off, const uint8_t* d_written,
+                               const uint8_t* d_keep_live, const uint8_t* d_keep_op, const uint64_t* nwritten,
+                               const uint64_t* nkeep_live, const uint64_t* nkeep_op)
+{
+	if (!ctx || !nwritten || !nkeep_live || !nkeep_op)
+		return ArgStatus{SYZSIG_EINVAL, "db_apply: NULL argument"};
+	if (nl > kSigsMaxBatch || m > kSigsMaxBatch || nl + m > kSigsMaxBatch)
+		return ArgStatus{SYZSIG_ERANGE, "db_apply: more than 2^25 records and ops in one call"};
+	if (nl && (!d_live_sig || !d_live_seq || !d_live_off || !d_keep_live || (live_bytes && !d_live_data)))
+		return ArgStatus{SYZSIG_EINVAL, "db_apply: NULL argument"};
+	if (m && (!d_op_sig || !d_op_seq || !d_op_off || !d_written || !d_keep_op || (op_bytes && !d_op_data)))
+		return ArgStatus{SYZSIG_EINVAL, "db_apply: NULL argument"};
+	return arg_ok();
+}
+
+// ... and after: offsets that decrease or pass their nbytes, deletes with a value, live seqs of ^0
+inline ArgStatus db_apply_status(uint64_t bad, uint64_t del_with_val, uint64_t live_deleted)
+{
+	if (bad)
+		return ArgStatus{SYZSIG_EINVAL, "db_apply: the offsets decrease or pass their nbytes"};
+	if (del_with_val)
+		return ArgStatus{SYZSIG_EINVAL, "db_apply: deleting record with value"};
+	if (live_deleted)
+		return ArgStatus{SYZSIG_EINVAL, "db_apply: a live record with the reserved seq"};
+	return arg_ok();
+}
+
 inline ArgStatus db_live_args(const void* ctx, const uint8_t* d_sig, const uint64_t* d_seq, uint64_t n, uint64_t nvalid,
                               const uint8_t* d_live, const uint64_t* nlive, const uint64_t* uncompacted)
 {

@@ -209,7 +209,8 @@ enum WsSlot : int {
 	kWsRcMeta = 75,
 	kWsRcStage = 76,
 	kWsRcStage2 = 77,
-	// db.hip: the long streams' list | the statuses, lengths and offsets held back until the call's end
+	// db.hip: the long streams' (values') list | the statuses, lengths and offsets held back until the call's
+	// end (inflate, deflate, db_records)
 	kWsInfList = 78,
 	kWsInfMeta = 79,
 	// calls.hip: the tiles' line counts and bases, the programs' first lines and held-back outputs | the
@@ -287,6 +288,7 @@ struct syzsig_ctx {
 	uint64_t rc_stats[4] = {0, 0, 0, 0};  // syzsig_report_stats: the last coverage-report call's paths (report.hip)
 	uint64_t fs_stats[4] = {0, 0, 0, 0};  // syzsig_file_set_stats: the last file_set call's paths (report.hip)
 	uint64_t if_stats[4] = {0, 0, 0, 0};  // syzsig_inflate_stats: the last inflate call's paths (db.hip)
+	uint64_t df_stats[4] = {0, 0, 0, 0};  // syzsig_deflate_stats: the last deflate call's paths (db.hip)
 	uint64_t pc_stats[4] = {0, 0, 0, 0};  // syzsig_prog_calls_stats: the last prog_calls call's paths (calls.hip)
 	bool hash_stage = true;             // syzsig_hash_dev stages a wave's span in LDS (SYZSIG_HASH_STAGE=0: never, for A/B)
 };

@@ -1,8 +1,9 @@
 // sigs.hip -- corpus identity on device: pkg/hash over a batch of programs
 // (syzsig_hash_dev) and the sets keyed by hash.Sig (syzsig_sigset_*,
 // syzsig_number_sigs_dev, syzsig_hub_sync_dev), and on the same sort the
-// last-write-wins of pkg/db's replay (syzsig_db_live_dev; the rest of pkg/db is
-// db.hip).
+// last-write-wins of pkg/db's replay (syzsig_db_live_dev) and its Save / Delete
+// over a batch (syzsig_db_apply_dev, at the end of this file); the rest of
+// pkg/db is db.hip.
 //
 // References:
 //   pkg/hash/hash.go:14-26    type Sig [sha1.Size]byte; Hash = sha1 of the pieces
@@ -461,6 +462,27 @@ static int sg_work(syzsig_ctx* ctx, uint64_t L, uint64_t n, SgWork* w)
 	return SYZSIG_OK;
 }
 
+// The n keys packed into bb, with w's tile table, sorted through ba: *sorted, and *spare = the other buffer.
+static int sg_sort_packed(syzsig_ctx* ctx, uint64_t n, const SgWork& w, uint64_t* ba, uint64_t* bb,
+                          const uint64_t** sorted, uint64_t** spare = nullptr)
+{
+	const hipStream_t s = ctx->stream;
+	const uint64_t nt = (n + kSgTile - 1) / kSgTile;
+	const SuSegs S{bb, 3, w.tab.src_start, w.tab.len, 1, w.tab.len, 1};
+	const SuTiles T{nullptr, w.tab.base, w.tab.len, w.tab.owner, w.tab.idx, 1, nt};
+	uint64_t *src = ba, *dst = bb;
+	k_su_tile_sort<SgTile><<<grid_cap(nt), kSuThreads, 0, s>>>(S, T, src, nullptr);
+	for (uint64_t width = kSgTile; width < n; width <<= 1) {
+		k_su_merge<SgKey, kSgTile><<<grid_cap(nt), kSuThreads, 0, s>>>(T, width, src, dst, nullptr);
+		std::swap(src, dst);
+	}
+	SYZ_HIP(hipGetLastError());
+	*sorted = src;
+	if (spare)
+		*spare = dst;
+	return SYZSIG_OK;
+}
+
 // The batch's keys (Sig, row) sorted: *sorted; *spare = the other buffer, n keys of room.  Enqueues only.
 static int sg_sort(syzsig_ctx* ctx, const uint8_t* d_sig, uint64_t n, const SgWork& w, const uint64_t** sorted,
                    uint64_t** spare)
@@ -471,18 +493,7 @@ static int sg_sort(syzsig_ctx* ctx, const uint8_t* d_sig, uint64_t n, const SgWo
 	SYZ_TRY(ws_get(ctx, kWsSgBufA, n * 24 + 256, &ba));
 	SYZ_TRY(ws_get(ctx, kWsSgBufB, n * 24 + 256, &bb));
 	k_sg_pack<<<grid_for(std::max(n, nt), 256), 256, 0, s>>>(d_sig, n, (uint64_t*)bb, w.tab, nt);
-	const SuSegs S{bb, 3, w.tab.src_start, w.tab.len, 1, w.tab.len, 1};
-	const SuTiles T{nullptr, w.tab.base, w.tab.len, w.tab.owner, w.tab.idx, 1, nt};
-	uint64_t *src = (uint64_t*)ba, *dst = (uint64_t*)bb;
-	k_su_tile_sort<SgTile><<<grid_cap(nt), kSuThreads, 0, s>>>(S, T, src, nullptr);
-	for (uint64_t width = kSgTile; width < n; width <<= 1) {
-		k_su_merge<SgKey, kSgTile><<<grid_cap(nt), kSuThreads, 0, s>>>(T, width, src, dst, nullptr);
-		std::swap(src, dst);
-	}
-	SYZ_HIP(hipGetLastError());
-	*sorted = src;
-	*spare = dst;
-	return SYZSIG_OK;
+	return sg_sort_packed(ctx, n, w, (uint64_t*)ba, (uint64_t*)bb, sorted, spare);
 }
 
 // r[i] = the set flags of f before i; *total = all of them.  Synchronizes.
@@ -801,5 +812,196 @@ extern "C" int syzsig_db_live_dev(syzsig_ctx* ctx, const uint8_t* d_sig, const u
 	SYZ_HIP(hipStreamSynchronize(s));
 	*nlive = ctx->h_cnt[kCntInserted];
 	*uncompacted = nvalid;
+	return SYZSIG_OK;
+}
+
+// ---- Save and Delete over a batch (pkg/db/db.go:55-74) ----
+//
+// The rows are the nl live records, then the m ops: row r < nl is live record
+// r, row nl + j is op j.  Sorted by (Sig, row), a run holds a key's rows in the
+// order the reference would have met them, and what an op sees is what the row
+// before it in the run left -- whether or not that row was itself a no-op.
+//   k_ap_check    the two offset arrays, the deletes' values, the live seqs
+//   k_ap_pack     k_sg_pack over the two Sig arrays
+//   k_ap_written  per sorted row: does it reach the log (a live record does by
+//                 definition)?  A Save is compared with its predecessor byte by
+//                 byte only where seq and length agree
+//   k_ap_keep     per sorted row that is written and no delete: is every later
+//                 row of its run a no-op?  Then it is the key's record.
+
+namespace syz {
+
+struct ApRows {
+	const uint64_t *lseq, *loff, *oseq, *ooff;
+	const uint8_t *ldata, *odata;
+	uint64_t nl;
+	__device__ __forceinline__ uint64_t seq(uint64_t r) const { return r < nl ? lseq[r] : oseq[r - nl]; }
+	__device__ __forceinline__ const uint8_t* val(uint64_t r, uint64_t& len) const
+	{
+		const uint64_t* off = r < nl ? loff + r : ooff + (r - nl);
+		len = off[1] - off[0];
+		return (r < nl ? ldata : odata) + off[0];
+	}
+};
+
+__global__ __launch_bounds__(256) void k_ap_check(ApRows R, uint64_t m, uint64_t lbytes, uint64_t obytes,
+                                                  unsigned long long* cnt)
+{
+	const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
+	uint64_t bad = 0, delv = 0, ldel = 0;
+	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < R.nl + m; r += T) {
+		const bool live = r < R.nl;
+		const uint64_t* off = live ? R.loff + r : R.ooff + (r - R.nl);
+		const uint64_t a = off[0], b = off[1];
+		if (a > b || b > (live ? lbytes : obytes))
+			bad++;
+		else if (R.seq(r) != kDbSeqDeleted)
+			continue;
+		else if (live)
+			ldel++;
+		else
+			delv += b != a;
+	}
+	block_count(&cnt[kCntError], bad);
+	block_count(&cnt[kCntAux], delv);
+	block_count(&cnt[kCntTouched], ldel);
+}
+
+__global__ __launch_bounds__(256) void k_ap_pack(const uint8_t* __restrict__ lsig, uint64_t nl,
+                                                 const uint8_t* __restrict__ osig, uint64_t n, uint64_t* keys, SgTable t,
+                                                 uint64_t ntiles)
+{
+	const uint64_t T = (uint64_t)gridDim.x * blockDim.x, i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	for (uint64_t i = i0; i < n; i += T)
+		SgKey::put(keys, i, i < nl ? sg_load(lsig, i, (uint32_t)i) : sg_load(osig, i - nl, (uint32_t)i));
+	for (uint64_t i = i0; i < ntiles; i += T) {
+		t.owner[i] = 0;
+		t.idx[i] = (uint32_t)i;
+	}
+	if (i0 == 0) {
+		*t.base = 0;
+		*t.src_start = 0;
+		*t.len = (uint32_t)n;
+	}
+}
+
+// wr[j] = sorted row j reaches the log (or is a live record); row_written[op] for the ops
+__global__ __launch_bounds__(256) void k_ap_written(const uint64_t* __restrict__ b, uint64_t n, ApRows R, uint32_t* wr,
+                                                    uint8_t* row_written, unsigned long long* cnt)
+{
+	const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
+	uint64_t k = 0;
+	for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += T) {
+		const SgT x = SgKey::get(b, j);
+		const uint64_t r = sg_row(x);
+		if (r < R.nl) {
+			wr[j] = 1;
+			continue;
+		}
+		const uint64_t sq = R.seq(r);
+		bool present = false;
+		uint64_t p = 0;
+		if (j > 0) {
+			const SgT y = SgKey::get(b, j - 1);
+			p = sg_row(y);
+			present = sg_same(x, y) && R.seq(p) != kDbSeqDeleted;
+		}
+		bool w;
+		if (sq == kDbSeqDeleted) {
+			w = present;  // db.go:68-70
+		} else {
+			w = true;
+			if (present && R.seq(p) == sq) {  // db.go:59-61
+				uint64_t la, lb;
+				const uint8_t *va = R.val(p, la), *vb = R.val(r, lb);
+				if (la == lb) {
+					uint64_t i = 0;
+					while (i < la && va[i] == vb[i])
+						i++;
+					w = i < la;
+				}
+			}
+		}
+		wr[j] = w;
+		row_written[r - R.nl] = w;
+		k += w;
+	}
+	block_count(cnt, k);
+}
+
+// keep[row] = 1 iff the row is written, no delete, and every later row of its run is a no-op
+__global__ __launch_bounds__(256) void k_ap_keep(const uint64_t* __restrict__ b, uint64_t n, ApRows R,
+                                                 const uint32_t* __restrict__ wr, uint8_t* row_keep,
+                                                 unsigned long long* cnt_live, unsigned long long* cnt_op)
+{
+	const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
+	uint64_t kl = 0, ko = 0;
+	for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += T) {
+		const SgT x = SgKey::get(b, j);
+		const uint64_t r = sg_row(x);
+		bool keep = wr[j] && R.seq(r) != kDbSeqDeleted;
+		for (uint64_t q = j + 1; keep && q < n && sg_same(x, SgKey::get(b, q)); q++)
+			keep = !wr[q];
+		row_keep[r] = keep;
+		(r < R.nl ? kl : ko) += keep;
+	}
+	block_count(cnt_live, kl);
+	block_count(cnt_op, ko);
+}
+
+}  // namespace syz
+
+extern "C" int syzsig_db_apply_dev(syzsig_ctx* ctx, const uint8_t* d_live_sig, const uint64_t* d_live_seq, uint64_t nl,
+                                   const uint8_t* d_live_data, uint64_t live_bytes, const uint64_t* d_live_off,
+                                   const uint8_t* d_op_sig, const uint64_t* d_op_seq, uint64_t m,
+                                   const uint8_t* d_op_data, uint64_t op_bytes, const uint64_t* d_op_off,
+                                   uint8_t* d_written, uint8_t* d_keep_live, uint8_t* d_keep_op, uint64_t* nwritten,
+                                   uint64_t* nkeep_live, uint64_t* nkeep_op)
+{
+	SYZ_LOCK(ctx);
+	for (uint64_t* c : {nwritten, nkeep_live, nkeep_op})
+		if (c)
+			*c = 0;
+	SYZ_ARGS(db_apply_args(ctx, d_live_sig, d_live_seq, nl, d_live_data, live_bytes, d_live_off, d_op_sig, d_op_seq, m,
+	                       d_op_data, op_bytes, d_op_off, d_written, d_keep_live, d_keep_op, nwritten, nkeep_live,
+	                       nkeep_op));
+	const uint64_t n = nl + m;
+	if (n == 0)
+		return SYZSIG_OK;
+	const hipStream_t s = ctx->stream;
+	const ApRows R{d_live_seq, d_live_off, d_op_seq, d_op_off, d_live_data, d_op_data, nl};
+	SYZ_TRY(counters_reset(ctx));
+	k_ap_check<<<grid_for(n, 256), 256, 0, s>>>(R, m, live_bytes, op_bytes, ctx->d_cnt);
+	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(counters_fetch(ctx));
+	SYZ_ARGS(db_apply_status(ctx->h_cnt[kCntError], ctx->h_cnt[kCntAux], ctx->h_cnt[kCntTouched]));
+	uint8_t* stage;  // row_keep[n], then row_written[m]: held back until nothing can fail
+	SYZ_TRY(ws_get(ctx, kWsSgOut, n + m + 512, (void**)&stage));
+	uint8_t *row_keep = stage, *row_written = stage + align256(n);
+	SgWork w;
+	SYZ_TRY(sg_work(ctx, n, n, &w));
+	const uint64_t nt = (n + kSgTile - 1) / kSgTile;
+	void *ba, *bb;
+	SYZ_TRY(ws_get(ctx, kWsSgBufA, n * 24 + 256, &ba));
+	SYZ_TRY(ws_get(ctx, kWsSgBufB, n * 24 + 256, &bb));
+	SYZ_TRY(counters_reset(ctx));
+	k_ap_pack<<<grid_for(std::max(n, nt), 256), 256, 0, s>>>(d_live_sig, nl, d_op_sig, n, (uint64_t*)bb, w.tab, nt);
+	const uint64_t* b;
+	SYZ_TRY(sg_sort_packed(ctx, n, w, (uint64_t*)ba, (uint64_t*)bb, &b));
+	k_ap_written<<<grid_for(n, 256), 256, 0, s>>>(b, n, R, w.f0, row_written, &ctx->d_cnt[kCntInserted]);
+	k_ap_keep<<<grid_for(n, 256), 256, 0, s>>>(b, n, R, w.f0, row_keep, &ctx->d_cnt[kCntChanged],
+	                                           &ctx->d_cnt[kCntCandidates]);
+	SYZ_HIP(hipGetLastError());
+	SYZ_TRY(counters_fetch(ctx));
+	if (nl)
+		SYZ_HIP(hipMemcpyAsync(d_keep_live, row_keep, nl, hipMemcpyDeviceToDevice, s));
+	if (m) {
+		SYZ_HIP(hipMemcpyAsync(d_keep_op, row_keep + nl, m, hipMemcpyDeviceToDevice, s));
+		SYZ_HIP(hipMemcpyAsync(d_written, row_written, m, hipMemcpyDeviceToDevice, s));
+	}
+	SYZ_HIP(hipStreamSynchronize(s));
+	*nwritten = ctx->h_cnt[kCntInserted];
+	*nkeep_live = ctx->h_cnt[kCntChanged];
+	*nkeep_op = ctx->h_cnt[kCntCandidates];
 	return SYZSIG_OK;
 }
